@@ -14,7 +14,7 @@ GIT_DESCRIBE ?= $(shell git describe --always --long --dirty 2>/dev/null || echo
 DOCKER ?= docker
 BUILD_ARGS = --build-arg GIT_DESCRIBE=$(GIT_DESCRIBE)
 
-.PHONY: images push native test test-gpu sanitizers coverage fuzz bench
+.PHONY: images push native test test-gpu sanitizers coverage fuzz bench bench-full
 
 images:
 	$(DOCKER) build $(BUILD_ARGS) -f Dockerfile -t $(IMAGE_REPO):$(VERSION) .
@@ -53,3 +53,7 @@ fuzz:
 # the headline benchmark on this node (needs an MI355X)
 bench:
 	python3 bench.py --gpus 1 --steps 20 --warmup 3
+
+# the same with every secondary measurement (comparisons, peer probe, throughput check)
+bench-full:
+	python3 bench.py --gpus 1 --steps 20 --warmup 3 --full

@@ -33,7 +33,14 @@ The plugin is the real one: by default the native daemon mi355x-device-plugin
 CRI runtime are stand-ins (see rocm_k8s_device_plugin_amd/testing/
 fake_kubelet.py, container_runtime.py).
 
-  python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the result line.
+Everything else the benchmark measures (the comparison admissions in the
+other container modes / views / runtimes, the allocator microbenchmark, fabric
+and allocation reports, RCCL collectives, the peer probe, the throughput check)
+runs after the timed steps with --full only. --dump-outputs DIR writes what the
+last timed step returned (allocation and container verdicts) as .npy arrays.
+
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 """
 from __future__ import annotations
@@ -132,6 +139,14 @@ def make_parser():
                     help="seconds after the timed loop for every secondary measurement (comparisons, RCCL, peer "
                          "probe, throughput check); past it rank 0 prints the headline line with what it has and "
                          "every rank exits 0, so a hung extra cannot take the measured headline with it (0 = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take every secondary measurement (comparison admissions, "
+                         "allocator microbenchmark, fabric / allocation reports, health-loop report, RCCL, peer "
+                         "probe, throughput check) and report them in extra; off: the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float64): the allocation, the container's device view and its "
+                         "per-GPU MFMA liveness verdicts")
     ap.add_argument("--json-out", default="")
     return ap
 
@@ -202,6 +217,44 @@ def result_line(args, d, n, m_adv, held, plugin_kind, elapsed, latency_ms, extra
     })
 
 
+def dump_outputs(out_dir: str, d, adm, node) -> None:
+    """The last timed step's results as float64 arrays, written by rank 0 (every
+    rank contributes its container's part), identical from run to run with the
+    same arguments (nothing timed, no nonce, no PCI address):
+
+    allocated_devices.npy   per allocated device id, in the Allocate response's
+                            order: its position among the advertised devices
+    device_specs.npy        per allocated GPU: how many of the container's device
+                            nodes (DeviceSpecs) belong to it; then, per container
+                            process in rank order, the GPUs its runtime enumerated
+    containers_ready.npy    per container process: 1.0 = ready (every tile verified)
+    liveness.npy            per GPU of every container, in rank order, one row:
+                            ordinal in the container, ok, mismatching tile elements
+                            (of 32x32), runtime error code, MFMA iterations
+    """
+    doc = adm.last_doc if adm.args.steps > 0 else {}
+    mine = ([[dv.get("ordinal", -1), 1.0 if dv.get("ok") else 0.0, dv.get("mismatches", -1),
+              dv.get("hip_error", dv.get("hsa_error", 0)), dv.get("iters", -1)] for dv in doc.get("devices", [])],
+            [doc["hip_device_count"]] if "hip_device_count" in doc else [])
+    parts = d.gather(mine)   # pod mode: rank 0's container only; per-gpu: one container per rank
+    if d.rank != 0:
+        return
+    import numpy as np
+    last = adm.last
+    if last is None:
+        raise RuntimeError("--dump-outputs needs at least one timed step")
+    os.makedirs(out_dir, exist_ok=True)
+    adv = [dv.id for dv in node.adv]
+    arrays = {
+        "allocated_devices": [adv.index(i) for i in last["device_ids"]],
+        "device_specs": [len(g) for g in last["spec_groups"]] + [c for _, counts in parts for c in counts],
+        "containers_ready": [1.0 if ok else 0.0 for ok in last["containers_ok"]],
+        "liveness": np.asarray([r for rows, _ in parts for r in rows], dtype=np.float64).reshape(-1, 5),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -245,8 +298,8 @@ def main():
     elapsed = d.max(elapsed)
     rank_gpu_state = d.gather(adm.gpu_state)
 
-    # the headline is measured: from here on everything is bounded by the guard
-    guard = ExtrasGuard(d.rank, args.extras_deadline)
+    # the headline is measured: from here on (--full) everything is bounded by the guard
+    guard = ExtrasGuard(d.rank, args.extras_deadline if args.full else 0.0)
     if d.rank == 0:
         from rocm_k8s_device_plugin_amd.benchmark.stats import pct
         guard.kill_on_fire(plug)
@@ -282,7 +335,11 @@ def main():
         guard.fallback = partial_line
 
     try:
-        extra = Extras(args, d, n, adm, guard, node).run()
+        if args.dump_outputs:
+            # inside the guard: a dump that fails (an unwritable DIR) is reported, the headline still printed
+            guard.enter("dump_outputs")
+            dump_outputs(args.dump_outputs, d, adm, node)
+        extra = Extras(args, d, n, adm, guard, node).run() if args.full else {}
         if d.rank == 0:
             guard.enter("plugin_stop")
             plug.stop()

@@ -2,9 +2,11 @@
 // -fsanitize=address,undefined / thread (MI355X_SANITIZE) — the reference has
 // no race or sanitizer coverage at all.
 //
-//   test_core <repo testdata dir> [<reference testdata dir>]
+//   test_core <repo testdata dir> <captures dir>
 //
-// Reference fixtures are optional: missing => those cases are skipped.
+// <captures dir>: the captured kfd topology / debugfs trees of
+// tests/golden/reference/testdata.tar.xz, unpacked (CMake does it for ctest).
+// A missing capture is a failure.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -82,10 +84,8 @@ static std::set<std::string> as_set(const std::vector<std::string>& v) { return 
 
 static void test_parsers(const std::string& ref) {
   auto kv = parse_kv_file(ref + "/topology-parsing/topology/nodes/2/properties");
-  if (!kv) {
-    ++g_skip;
-    return;
-  }
+  CHECK(kv.has_value());
+  if (!kv) return;
   CHECK(kv_i64(*kv, "simd_count", 0) == 256);
   CHECK(kv_i64(*kv, "simd_id_base", 0) == 2147487744LL);
   CHECK(kv->find("asdf") == kv->end());
@@ -104,10 +104,8 @@ static void test_parsers(const std::string& ref) {
 
 static void test_allocator_reference_contract(const std::string& ref) {
   auto topo = KfdTopology::load(ref + "/topo-mi300-cpx/topology/nodes");
-  if (topo.nodes().empty()) {
-    ++g_skip;
-    return;
-  }
+  CHECK(!topo.nodes().empty());
+  if (topo.nodes().empty()) return;
   auto devs = synthetic_devices(8, 8, 2, 2, 64);
   HiveAllocator a;
   CHECK(a.init(devs, topo).empty());
@@ -179,10 +177,8 @@ static void test_errors() {
 // reference BFS still agree on the re-weighted matrix.
 static void test_degraded_links(const std::string& ref) {
   auto topo = KfdTopology::load(ref + "/topo-mi210-xgmi-pcie/nodes");
-  if (topo.nodes().empty()) {
-    ++g_skip;
-    return;
-  }
+  CHECK(!topo.nodes().empty());
+  if (topo.nodes().empty()) return;
   auto devs = synthetic_devices(8, 1, 2, 1, 8);
   HiveAllocator a;
   CHECK(a.init(devs, topo).empty());
@@ -589,9 +585,10 @@ static void test_fuzz_rpc(const std::string& ref) {
   CHECK(fd >= 0 && ::write(fd, req.data(), req.size()) == static_cast<ssize_t>(req.size()) &&
         h2t::read_call(fd, 1, &r, &dec) && r.grpc_status == 0 && r.messages.size() == 1);
   // well-formed calls with random / mutated protobuf bodies: every one gets a
-  // gRPC status (the allocator on the reference's MI300X CPX capture when present)
+  // gRPC status (the allocator on the reference's MI300X CPX capture)
   auto topo = KfdTopology::load(ref + "/topo-mi300-cpx/topology/nodes");
   const auto devs = synthetic_devices(8, 8, 2, 2, 64);
+  CHECK(!topo.nodes().empty());
   if (!topo.nodes().empty()) {
     auto a = std::make_shared<HiveAllocator>();
     CHECK(a->init(devs, topo).empty());
@@ -1081,7 +1078,7 @@ static void test_health_controller_generations(const std::string& tmp) {
 
 int main(int argc, char** argv) {
   std::string repo = argc > 1 ? argv[1] : "testdata";
-  std::string ref = argc > 2 ? argv[2] : "/root/reference/testdata";
+  std::string ref = argc > 2 ? argv[2] : "build/native/reference/testdata";
   (void)repo;
   test_parsers(ref);
   test_allocator_reference_contract(ref);

@@ -105,6 +105,9 @@ class Admissions:
         self.rec = StepRecords()
         # worst seen in the timed loop: does a bench / plugin process hold the GPU?
         self.gpu_state = {"torch_cuda_initialized": False, "kfd_fds": 0, "render_fds": 0}
+        # what the last timed step returned to its caller (bench.py --dump-outputs)
+        self.last_doc: dict = {}
+        self.last: Optional[dict] = None
 
     # ------------------------------------------------------------------ helpers
     def _blocking(self, fn, *a, **kw):
@@ -147,6 +150,7 @@ class Admissions:
         stub = dict(exe=STUB_PROBE, argv_prefix=[sys.executable]) if a_.fixture else {}
         r = self._blocking(start_container, mine_ord, timeout_s=a_.container_timeout, runtime=runtime,
                            mounts=mounts if not a_.fixture else (), device_paths=paths, **stub)
+        self.last_doc = r.doc
         devs = r.doc.get("devices", [])
         kus = max((dv.get("kernel_us", 0.0) for dv in devs), default=0.0)
         # device set-up (HIP: hipSetDevice .. stream/buffers/events; HSA: queue, code object, buffers)
@@ -206,6 +210,9 @@ class Admissions:
             raise SystemExit(f"container failed to become ready: {bad[0]}")
         slowest = max(allr, key=lambda m: m[1])
         t_ready = slowest[1]
+        if record is True:
+            self.last = {"device_ids": list(ids), "spec_groups": groups, "containers_ok": [bool(m[0]) for m in allr],
+                         "doc": self.last_doc}
         if d.rank == 0:
             pl.kubelet.release("amd.com/gpu", ids)
         # pod termination: the driver finishes tearing down each container's kfd

@@ -17,7 +17,7 @@ looks like — XCDs, CUs, HBM, xGMI links, partition modes — so that
 Every entry says where its numbers come from: ``measured`` = read on a real
 MI355X gpurun box (profiles/archive/real_sysfs_inventory_box.json,
 amdsmi_snapshot_box.json, drm_info_box.json); ``reference-fixture`` = the
-captured sysfs trees under /root/reference/testdata (SURVEY §2.1 C28);
+captured sysfs trees of tests/golden/reference (SURVEY §2.1 C28);
 ``spec`` = vendor specification, not verified here.
 """
 from __future__ import annotations

@@ -416,3 +416,20 @@ def wrap_kfd_topology(topology_dir: os.PathLike, root: os.PathLike) -> FixtureIn
         info.render_minors[bdf] = minor
         info.node_ids[bdf] = int(nd.name)
     return info
+
+
+def reference_captures() -> str:
+    """The reference project's captured kfd topology / debugfs trees
+    (tests/golden/reference/testdata.tar.xz), unpacked into a temporary
+    directory that is removed at exit; returns its testdata/ directory."""
+    import atexit
+    import os
+    import shutil
+    import tarfile
+    import tempfile
+    repo = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    d = tempfile.mkdtemp(prefix="mi355x-captures-")
+    atexit.register(shutil.rmtree, d, True)
+    with tarfile.open(os.path.join(repo, "tests", "golden", "reference", "testdata.tar.xz")) as tar:
+        tar.extractall(d)
+    return os.path.join(d, "testdata")

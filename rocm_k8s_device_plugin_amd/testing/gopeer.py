@@ -5,8 +5,8 @@ RPC and the *server* of Registration (the metrics exporter is a grpc-go
 server too). The native HTTP/2 stack (native/src/rpc/grpc_server.cpp, grpc_client.cpp) must
 therefore interoperate with grpc-go's transport, which no Go toolchain here
 can run. These peers replay, frame by frame, what that transport does, taken
-from the vendored sources (reference paths below are under
-/root/reference/vendor/):
+from the reference's vendored sources (the paths below are under its
+vendor/ directory):
 
 client (``GoClientConn``, google.golang.org/grpc/internal/transport/http2_client.go)
   * connection preface, then a SETTINGS frame with no entries when the default

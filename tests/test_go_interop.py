@@ -41,7 +41,6 @@ from rocm_k8s_device_plugin_amd.testing import gopeer as gp
 from rocm_k8s_device_plugin_amd.testing.fixtures import make_mi355x_node
 
 EXE = os.environ.get("MI355X_NATIVE_DAEMON_EXE") or os.path.join(str(PKG_DIR), "bin", "mi355x-device-plugin")
-XNET = "/root/reference/vendor/golang.org/x/net/http2/hpack"
 DP = "/v1beta1.DevicePlugin/"
 REGISTER = "/v1beta1.Registration/Register"
 
@@ -65,31 +64,27 @@ def _wait(cond, timeout=10.0, step=0.02):
 
 # ------------------------------------------------------------------ the peers' own HPACK
 
-def _xnet(name):
-    path = os.path.join(XNET, name)
-    if not os.path.exists(path):
-        pytest.skip("vendored x/net sources not available")
-    with open(path) as f:
-        return f.read()
+def _xnet():
+    """x/net's hpack tables (huffmanCodes, huffmanCodeLen, the static table and its
+    by-name index), recorded in tests/golden/reference/hpack_tables.json."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "hpack_tables.json")) as f:
+        return json.load(f)
 
 
 def test_huffman_code_equals_xnet_tables():
     """The peers' canonical code (from RFC 7541 code lengths) is x/net's table."""
-    src = _xnet("tables.go")
-    codes = src[src.index("var huffmanCodes"):src.index("var huffmanCodeLen")]
-    lens = src[src.index("var huffmanCodeLen"):]
-    codes = [int(x, 16) for x in re.findall(r"0x[0-9a-f]+", codes)]
-    lens = [int(x) for x in re.findall(r"\b\d+\b", lens[lens.index("{"):lens.index("}")])]
+    t = _xnet()
+    codes, lens = t["huffman_codes"], t["huffman_code_len"]
     assert len(codes) == 256 and len(lens) == 256
     assert gp.HUFF_CODE[:256] == codes and list(gp.HUFF_LEN[:256]) == lens
 
 
 def test_static_table_and_name_index_equal_xnet():
-    src = _xnet("static_table.go")
-    ents = re.findall(r'\{Name: "([^"]*)", Value: "([^"]*)", Sensitive: false\}', src)
-    assert tuple(ents) == gp.STATIC_TABLE
-    by_name = dict(re.findall(r'^\s*"([^"]+)":\s+(\d+),$', src[:src.index("byNameValue")], re.M))
-    assert {k: int(v) for k, v in by_name.items()} == gp._STATIC_NAME
+    t = _xnet()
+    assert len(t["static_table"]) == 61
+    assert tuple(tuple(e) for e in t["static_table"]) == gp.STATIC_TABLE
+    assert t["static_name_index"] == gp._STATIC_NAME
 
 
 def test_go_encoder_rfc7541_c4_request():

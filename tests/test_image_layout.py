@@ -1,6 +1,6 @@
 """Every deploy path runs from the image it names.
 
-The reference builds the image its manifests and chart use (/root/reference/
+The reference builds the image its manifests and chart use (its
 Dockerfile:14-33 -> k8s-ds-amdgpu-dp.yaml, helm/amd-gpu/values.yaml:7-11).
 Here, without a container runtime:
 

@@ -93,7 +93,7 @@ def test_bench_fixture_reports_fabric_and_collectives():
     env = dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--fixture", "--steps", "2",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -126,7 +126,7 @@ def test_bench_n_of_m_searches_inside_the_timed_step():
     availability, and picks the reference BFS's set."""
     env = dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1")
     p = subprocess.run([sys.executable, "bench.py", "--fixture", "--gpus", "3", "--advertise", "8", "--steps", "3",
-                        "--warmup", "1"], cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
+                        "--warmup", "1", "--full"], cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     ta = d["extra"]["timed_allocation"]
@@ -145,6 +145,38 @@ def test_bench_n_of_m_searches_inside_the_timed_step():
     assert all(s["latency_ms"] > ta["threshold_ms"] for s in ta["slow_steps"])
 
 
+def test_bench_plain_run_takes_no_secondary_measurement(tmp_path):
+    """Without --full: the headline line with the timed steps' own numbers and none
+    of the secondary measurements; --dump-outputs writes the last timed step's
+    results, the same arrays on every run with the same arguments."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1")
+    runs = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, "bench.py", "--fixture", "--gpus", "2", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / name)], cwd=REPO, env=env, capture_output=True,
+                           text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and len(d["extra"]["steps_ms"]) == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "ms" and d["higher_is_better"] is False and d["dtype"] == "fp32"
+        for key in ("comparisons", "fabric", "timed_allocation", "allocator_us", "rccl", "fragmented_n_of_m",
+                    "extras_incomplete"):
+            assert key not in d["extra"], key
+        runs.append({f.name: np.load(f) for f in sorted((tmp_path / name).iterdir())})
+    a, b = runs
+    assert set(a) == set(b) == {"allocated_devices.npy", "device_specs.npy", "containers_ready.npy", "liveness.npy"}
+    for k in a:
+        assert a[k].dtype == np.float64 and a[k].shape == b[k].shape and (a[k] == b[k]).all(), k
+    assert sorted(a["allocated_devices.npy"]) == [0.0, 1.0]
+    assert a["device_specs.npy"][-1] == 2 and (a["device_specs.npy"][:-1] >= 1).all()
+    assert a["containers_ready.npy"].tolist() == [1.0]
+    assert a["liveness.npy"].shape == (2, 5) and a["liveness.npy"][:, 1].tolist() == [1.0, 1.0]
+    assert a["liveness.npy"][:, 2].tolist() == [0.0, 0.0]
+
+
 def test_bench_python_plugin_option():
     """--plugin python: the Python CLI's plugin in the bench process serves the admissions."""
     env = dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1")
@@ -155,6 +187,11 @@ def test_bench_python_plugin_option():
     assert d["extra"]["plugin"] == "python" and d["extra"]["plugin_server_p50_us"]
 
 
+# comparison admissions that outlast any 0.5 s deadline, however fast the host: each of the
+# 400 starts a process (the deadline ends the run long before they are through)
+_SLOW_EXTRAS = ("--mode-compare", "200", "--fragmented-compare", "200")
+
+
 def test_bench_extras_deadline_keeps_the_headline():
     """A secondary measurement that overruns --extras-deadline (standing in for
     a hung RCCL communicator or DMA on a sick node): rank 0 still prints exactly
@@ -163,7 +200,7 @@ def test_bench_extras_deadline_keeps_the_headline():
     env = dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--fixture", "--steps", "2",
-           "--warmup", "1", "--extras-deadline", "0.5"]
+           "--warmup", "1", "--full", "--extras-deadline", "0.5", *_SLOW_EXTRAS]
     proc = subprocess.Popen(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                             start_new_session=True)   # its own process group: whatever it leaves is ours
     try:
@@ -205,9 +242,9 @@ def _bench_ranks(n, *args, torchrun=True, timeout=300):
     env = dict(os.environ, PYTHONPATH=REPO, OMP_NUM_THREADS="1")
     if torchrun:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nproc-per-node", str(n), "--master-addr",
-               "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(n), "--fixture", *args]
+               "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(n), "--fixture", "--full", *args]
     else:
-        cmd = [sys.executable, "bench.py", "--gpus", str(n), "--fixture", *args]
+        cmd = [sys.executable, "bench.py", "--gpus", str(n), "--fixture", "--full", *args]
     proc = subprocess.Popen(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                             start_new_session=True)
     t0 = time.monotonic()
@@ -253,7 +290,7 @@ def test_bench_torchrun_8_ranks_extras_deadline_fires():
     """At 8 ranks a deadline that fires inside the extras (rank 0 leaves while
     the others wait in a collective): still exactly one headline line, every
     rank exits 0, no daemon left."""
-    d, err = _bench_ranks(8, "--steps", "2", "--warmup", "1", "--extras-deadline", "0.5")
+    d, err = _bench_ranks(8, "--steps", "2", "--warmup", "1", "--extras-deadline", "0.5", *_SLOW_EXTRAS)
     e = d["extra"]
     inc = e["extras_incomplete"]
     assert inc["deadline_s"] == 0.5 and inc["stage"], inc

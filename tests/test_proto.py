@@ -1,26 +1,26 @@
 """Wire-contract parity: our hand-built descriptors vs the FileDescriptorProtos
-embedded in the reference's generated Go code (gogo api.pb.go, gzipped; and
-metricssvc.pb.go, raw). Field names, numbers, labels, types and the service
+embedded in the reference's generated Go code (gogo api.pb.go and
+metricssvc.pb.go). Field names, numbers, labels, types and the service
 method signatures must be identical for kubelet / the exporter to interoperate.
-The reference files are read as text; nothing from them is executed."""
-import gzip
-import re
+The reference's side is recorded in tests/golden/reference/proto_contract.json:
+what _fields / _services / the enum listing below give for its descriptors."""
+import json
+from pathlib import Path
 
-import pytest
 from google.protobuf import descriptor_pb2
 
 from rocm_k8s_device_plugin_amd.proto import deviceplugin as dp
 from rocm_k8s_device_plugin_amd.proto import metricssvc as ms
 
-API_PB = "vendor/k8s.io/kubelet/pkg/apis/deviceplugin/v1beta1/api.pb.go"
-MS_PB = "internal/pkg/exporter/metricssvc/metricssvc.pb.go"
+CONTRACT = json.loads((Path(__file__).resolve().parent / "golden/reference/proto_contract.json").read_text())
 
 
-def _go_bytes(text: str, var: str) -> bytes:
-    m = re.search(r"var " + re.escape(var) + r" = \[\]byte\{(.*?)\n\}", text, re.S)
-    assert m, var
-    body = re.sub(r"//[^\n]*", "", m.group(1))
-    return bytes(int(x, 16) for x in re.findall(r"0x[0-9a-fA-F]{2}", body))
+def _ref_fields(ref):
+    return {(m, f): (number, label, ftype, tn) for m, f, number, label, ftype, tn in ref["fields"]}
+
+
+def _ref_services(ref):
+    return {(s, m): (inp, out, sstream, cstream) for s, m, inp, out, sstream, cstream in ref["services"]}
 
 
 def _fields(fdp):
@@ -47,26 +47,24 @@ def _ours(desc):
     return fdp
 
 
-def test_deviceplugin_descriptor_matches_reference(ref_testdata):
-    src = (ref_testdata.parent / API_PB).read_text()
-    ref = descriptor_pb2.FileDescriptorProto.FromString(
-        gzip.decompress(_go_bytes(src, "fileDescriptor_00212fb1f9d3bf1c")))
+def test_deviceplugin_descriptor_matches_reference():
+    ref = CONTRACT["deviceplugin"]
     ours = _ours(dp.FILE_DESCRIPTOR)
-    assert ref.package == ours.package == "v1beta1"
-    assert _fields(ours) == _fields(ref)
-    assert _services(ours) == _services(ref)
+    assert ref["package"] == ours.package == "v1beta1"
+    assert len(ref["fields"]) > 30 and len(ref["services"]) == 6
+    assert _fields(ours) == _ref_fields(ref)
+    assert _services(ours) == _ref_services(ref)
 
 
-def test_metricssvc_descriptor_matches_reference(ref_testdata):
-    src = (ref_testdata.parent / MS_PB).read_text()
-    ref = descriptor_pb2.FileDescriptorProto.FromString(_go_bytes(src, "file_metricssvc_proto_rawDesc"))
+def test_metricssvc_descriptor_matches_reference():
+    ref = CONTRACT["metricssvc"]
     ours = _ours(ms.FILE_DESCRIPTOR)
-    assert ref.package == ours.package == "metricssvc"
-    assert _fields(ours) == _fields(ref)
-    assert _services(ours) == _services(ref)
-    assert [e.name for e in ref.enum_type] == [e.name for e in ours.enum_type]
-    assert [(v.name, v.number) for v in ref.enum_type[0].value] == [(v.name, v.number)
-                                                                    for v in ours.enum_type[0].value]
+    assert ref["package"] == ours.package == "metricssvc"
+    assert ref["fields"] and ref["services"]
+    assert _fields(ours) == _ref_fields(ref)
+    assert _services(ours) == _ref_services(ref)
+    assert [e["name"] for e in ref["enums"]] == [e.name for e in ours.enum_type]
+    assert [tuple(v) for v in ref["enums"][0]["values"]] == [(v.name, v.number) for v in ours.enum_type[0].value]
 
 
 def test_roundtrip_wire_bytes():

@@ -37,7 +37,6 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 from rocm_k8s_device_plugin_amd.allocator import BestEffortPolicy  # noqa: E402
 
-REF = "/root/reference/testdata"
 
 
 def mi355x_layouts(tmp):
@@ -57,10 +56,10 @@ def mi355x_layouts(tmp):
 
 
 def reference_layouts():
-    if not os.path.isdir(REF):
-        return {}
     from test_allocator import TOPOS, synthetic_devices
     from rocm_k8s_device_plugin_amd.allocator import load_topology
+    from rocm_k8s_device_plugin_amd.testing.fixtures import reference_captures
+    REF = reference_captures()
     out = {}
     for name in ("mi300cpx", "mi308"):
         t = TOPOS[name]

@@ -28,10 +28,9 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from rocm_k8s_device_plugin_amd.allocator import BestEffortPolicy, load_topology  # noqa: E402
-from rocm_k8s_device_plugin_amd.testing.fixtures import make_mi355x_node  # noqa: E402
+from rocm_k8s_device_plugin_amd.testing.fixtures import make_mi355x_node, reference_captures  # noqa: E402
 from rocm_k8s_device_plugin_amd.topology import discover  # noqa: E402
 
-REF = "/root/reference/testdata"
 
 
 def pct(xs, q):
@@ -166,6 +165,7 @@ def main():
             pol = BestEffortPolicy()
             pol.init(inv.devices, inv.topology)
             res["allocator"] += bench_topology(name, pol, [x.id for x in inv.devices], sizes, rng)
+        REF = reference_captures()
         if os.path.isdir(REF):
             for name, args, path, sizes in [
                 ("ref_mi210_2hives", (8, 1, 2, 2, 9), "topo-mi210-xgmi-pcie/nodes", range(1, 8)),

@@ -69,14 +69,14 @@ for s in "$@"; do
       cut -c1-600 gpurun_out/bench100.json ;;
     health)
       step health
-      timeout -k 10 400 python3 bench.py --steps 30 --health-pulse 2 --runtime-compare 0 \
+      timeout -k 10 400 python3 bench.py --full --steps 30 --health-pulse 2 --runtime-compare 0 \
         --json-out gpurun_out/bench_health.json > gpurun_out/bench_health.log 2>&1 \
         || { tail -20 gpurun_out/bench_health.log; exit 1; }
       python3 -c "import json; d=json.load(open('gpurun_out/bench_health.json')); print(d['value'], d['extra']['health_loop'])" ;;
     healthpre)
       # the health DaemonSet configuration plus -prestart_liveness (kubelet's PreStartContainer probes the pod's GPU)
       step healthpre
-      timeout -k 10 400 python3 bench.py --steps 30 --health-pulse 2 --health-prestart 1 --runtime-compare 0 \
+      timeout -k 10 400 python3 bench.py --full --steps 30 --health-pulse 2 --health-prestart 1 --runtime-compare 0 \
         --json-out gpurun_out/bench_health_prestart.json > gpurun_out/bench_health_prestart.log 2>&1 \
         || { tail -20 gpurun_out/bench_health_prestart.log; exit 1; }
       python3 -c "import json; d=json.load(open('gpurun_out/bench_health_prestart.json')); e=d['extra']; print(d['value'], e['plugin_rpc_p50_ms'], e['prestart_rpc_p50_ms'], e['health_loop'])" ;;
