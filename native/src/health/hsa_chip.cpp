@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "hsa_runtime.h"
+#include "probe_verify.h"
 
 using namespace mi355x::hsa_rt;  // NOLINT(build/namespaces)
 
@@ -389,7 +390,7 @@ extern "C" int mi355x_hsa_chip_sweep(int ordinal, uint32_t nonce, int iters, dou
           float dot = 0.f;
           for (int k = 0; k < MI355X_PROBE_K; ++k) dot += probe_a(i, k, nw) * probe_b(k, j, nw);
           const float e = probe_c(i, j, nw) + static_cast<float>(out->iters) * dot;
-          tb += tile[i * MI355X_PROBE_N + j] != e;
+          tb += !mi355x::same_bits(tile[i * MI355X_PROBE_N + j], e);
         }
       out->tile_bad += tb;
       if (r[MI355X_REC_MFMA_BAD] == 0 && r[MI355X_REC_LDS_BAD] == 0 && tb == 0) ++out->records_ok;

@@ -142,7 +142,8 @@ MI355X_HD uint32_t hbm_pattern(uint64_t word, uint32_t seed) {
   return (uint32_t)(word ^ (word >> 32)) * 0x9E3779B1u + seed;
 }
 
-// bf16 bit pattern of a pseudo-random operand in +-[2^-7, 2^-1): every MFMA
+// bf16 bit pattern of a pseudo-random operand in +-[2^-7, 1) (exponent field
+// 120..126, all 7 mantissa bits; largest magnitude 0.996): every MFMA
 // input bit toggles (zero or small-integer operands run at a higher clock than
 // real data, MI355X_MICROARCH.md "DVFS give-back")
 MI355X_HD uint16_t burn_bf16_bits(uint32_t lane, uint32_t j, uint32_t nonce) {

@@ -2,11 +2,21 @@
 #pragma once
 
 #include <cstdio>
+#include <cstring>
 
 #include "liveness_kernel.h"
 #include "mi355x/liveness_probe.h"
 
 namespace mi355x {
+
+// Bit patterns, not values: -0.0 == 0.0 as floats, so a flipped sign bit of a
+// zero element would pass a float compare.
+inline bool same_bits(float a, float b) {
+  uint32_t x, y;
+  std::memcpy(&x, &a, sizeof(x));
+  std::memcpy(&y, &b, sizeof(y));
+  return x == y;
+}
 
 inline void verify_tile(const float* out, const uint32_t* meta, uint32_t nonce, int iters,
                         mi355x_probe_result* r) {
@@ -16,7 +26,7 @@ inline void verify_tile(const float* out, const uint32_t* meta, uint32_t nonce, 
       float ab = 0.f;
       for (int k = 0; k < MI355X_PROBE_K; ++k) ab += probe_a(i, k, nonce) * probe_b(k, j, nonce);
       const float want = probe_c(i, j, nonce) + static_cast<float>(iters) * ab;
-      if (out[i * MI355X_PROBE_N + j] != want) ++mism;
+      if (!same_bits(out[i * MI355X_PROBE_N + j], want)) ++mism;
     }
   r->mismatches = mism;
   r->xcc_id = meta[MI355X_META_XCC];

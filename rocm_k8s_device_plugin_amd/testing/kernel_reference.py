@@ -1,0 +1,299 @@
+"""Independent references for the five gfx950 kernels of
+native/src/health/liveness_kernel.hip, and the comparisons the raw-output
+tests apply to what the kernels wrote.
+
+Pure Python ints and numpy; nothing native is imported. Written from the
+contract stated in liveness_kernel.h (operand formulas, record words, argument
+structs) and the MFMA register layouts of cdna_hip_programming.md section 3,
+not from the host verifiers: those share probe_a/b/c with the kernels, so
+they can only agree with themselves.
+
+All generator arithmetic is unsigned 32-bit: `i*3u + k*5u + nonce` wraps, and
+7, 5 and 4 do not all divide 2^32, so a reference that forgets the wrap
+differs near nonce 2^32 (0xFFFFFFF9 is in NONCES for that reason).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+M32 = 0xFFFFFFFF
+M64 = 0xFFFFFFFFFFFFFFFF
+
+PROBE_M = PROBE_N = 32
+PROBE_K = 2
+PROBE_MAGIC = 0x4D464D41   # "MFMA"
+SWEEP_MAGIC = 0x43484950   # "CHIP"
+PERF_MAGIC = 0x50455246    # "PERF"
+SWEEP_LDS_WORDS = 40960 - 16
+SCRATCH_FLOATS = 16 * 64
+REC_WORDS = 16
+NUM_XCC_MAX = 8            # an MI355X has 8 XCDs; a partition has fewer
+
+# liveness meta words
+META_MAGIC, META_NONCE, META_XCC, META_HWID = 0, 1, 2, 3
+# chip-sweep record words
+REC_MAGIC, REC_NONCE, REC_XCC, REC_HWID, REC_MFMA_BAD, REC_LDS_BAD, REC_ARRIVED = 0, 1, 2, 3, 4, 5, 6
+REC_T0_LO, REC_T0_HI, REC_T1_LO, REC_T1_HI, REC_WG = 7, 8, 9, 10, 11
+# mfma-burn record words
+PREC_MAGIC, PREC_WG, PREC_XCC, PREC_HWID = 0, 1, 2, 3
+PREC_RT0_LO, PREC_RT0_HI, PREC_RT1_LO, PREC_RT1_HI, PREC_CYC_LO, PREC_CYC_HI, PREC_NONCE, PREC_SUM = 4, 5, 6, 7, 8, 9, 10, 12
+
+NONCES = (0, 1, 6, 7, 34, 35, 12345, 0xDEADBEEF, 0xFFFFFFF9, 0xFFFFFFFF)
+ITERS = (1, 4, 64, 1 << 20)
+BURN_NONCES = (0, 1, 0xDEADBEEF, 0xFFFFFFFF)
+BURN_ITERS = (1, 2, 3)
+
+
+# ---- operand generators (mod 2^32) -------------------------------------------
+def probe_a(i: int, k: int, nonce: int) -> int:
+    return ((i * 3 + k * 5 + nonce) & M32) % 7 - 3
+
+
+def probe_b(k: int, j: int, nonce: int) -> int:
+    return ((j * 11 + k * 2 + nonce) & M32) % 5 - 2
+
+
+def probe_c(i: int, j: int, nonce: int) -> int:
+    return ((i + 2 * j + nonce) & M32) % 4
+
+
+def sweep_nonce(nonce: int, wg: int, wave: int) -> int:
+    return (nonce + wg * 4 + wave) & M32
+
+
+def sweep_lds_pattern(i: int, nonce: int, wg: int) -> int:
+    return ((i * 2654435761) & M32) ^ ((nonce + wg * 0x9E3779B1) & M32)
+
+
+def hbm_pattern(word: int, seed: int) -> int:
+    """32-bit word `word` (a 64-bit index) of the patterned buffer: the high
+    half of the index is folded into the low half before the multiply."""
+    return ((((word ^ (word >> 32)) & M32) * 0x9E3779B1) + seed) & M32
+
+
+def hbm_pattern_words(count: int, seed: int, first: int = 0) -> np.ndarray:
+    """hbm_pattern of `count` consecutive words as a uint32 array."""
+    w = np.arange(first, first + count, dtype=np.uint64)
+    x = (w ^ (w >> np.uint64(32))) & np.uint64(M32)
+    return ((x * np.uint64(0x9E3779B1) + np.uint64(seed)) & np.uint64(M32)).astype(np.uint32)
+
+
+def burn_bf16_bits(lane: int, j: int, nonce: int) -> int:
+    h = ((lane * 0x9E3779B1) & M32) ^ ((j * 0x85EBCA77) & M32) ^ nonce
+    h ^= h >> 15
+    h = (h * 0x2C1B3C6D) & M32
+    h ^= h >> 12
+    return (h & 0x807F) | ((120 + (h >> 8) % 7) << 7)
+
+
+def bf16_value(bits: int) -> float:
+    """The value of a bf16 bit pattern: a float32 whose low 16 bits are zero."""
+    return float(np.array([bits << 16], dtype=np.uint32).view(np.float32)[0])
+
+
+# ---- f32 tile (mi355x_mfma_liveness, mi355x_chip_sweep) ------------------------
+def tile_operands(nonce: int):
+    a = np.array([[probe_a(i, k, nonce) for k in range(PROBE_K)] for i in range(PROBE_M)], dtype=np.int64)
+    b = np.array([[probe_b(k, j, nonce) for j in range(PROBE_N)] for k in range(PROBE_K)], dtype=np.int64)
+    c = np.array([[probe_c(i, j, nonce) for j in range(PROBE_N)] for i in range(PROBE_M)], dtype=np.int64)
+    return a, b, c
+
+
+def tile(nonce: int, iters: int) -> np.ndarray:
+    """The exact 32x32 result C + iters * A.B, int64."""
+    a, b, c = tile_operands(nonce)
+    return c + iters * (a @ b)
+
+
+def tile_f32(nonce: int, iters: int) -> np.ndarray:
+    t = tile(nonce, iters)
+    assert np.abs(t).max() < 1 << 24      # so every partial sum is an exact fp32 number
+    return t.astype(np.float32)
+
+
+def scratch_image(t: np.ndarray) -> np.ndarray:
+    """The 16x64 float image the liveness kernel leaves in scratch: slot
+    r*64+lane is accumulator register r of lane `lane`, which holds
+    D[(r&3) + 8*(r>>2) + 4*(lane>>5)][lane&31]."""
+    img = np.empty((16, 64), dtype=np.float32)
+    for r in range(16):
+        for lane in range(64):
+            img[r, lane] = t[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)][lane & 31]
+    return img
+
+
+def wrong_tile_models(nonce: int, iters: int) -> dict:
+    """What plausible wrong kernels would produce instead of tile()."""
+    a, b, c = tile_operands(nonce)
+    t = c + iters * (a @ b)
+    rows = np.arange(PROBE_M)
+    return {
+        "transposed_output": t.T.copy(),
+        "ab_transposed": c + iters * (a @ b).T,
+        "k_swapped_in_a": c + iters * (a[:, ::-1] @ b),
+        "half_wave_rows_swapped": t[rows ^ 4].copy(),
+        "iters_plus_1": c + (iters + 1) * (a @ b),
+        "iters_minus_1": c + (iters - 1) * (a @ b),
+        "only_k0": c + iters * np.outer(a[:, 0], b[0, :]),
+        "c_dropped": iters * (a @ b),
+    }
+
+
+# ---- bf16 burn (mi355x_mfma_burn) ----------------------------------------------
+def burn_operands(nonce: int):
+    """A (32x16), B (16x32), C (32x16), D (16x32) as float64. Lane l holds, in
+    element j of its fragments, A[l&31][8*(l>>5)+j] and B[8*(l>>5)+j][l&31];
+    fragment x of a lane is burn_bf16_bits(l, j + 8*x), x = 0..3 for a, b, c, d."""
+    mats = [np.zeros((32, 16)), np.zeros((16, 32)), np.zeros((32, 16)), np.zeros((16, 32))]
+    for lane in range(64):
+        r, h = lane & 31, lane >> 5
+        for j in range(8):
+            for x in range(4):
+                v = bf16_value(burn_bf16_bits(lane, j + 8 * x, nonce))
+                if x % 2 == 0:
+                    mats[x][r, 8 * h + j] = v
+                else:
+                    mats[x][8 * h + j, r] = v
+    return mats
+
+
+def _burn_sums(a, b, c, d, iters):
+    checksum = iters * float((a @ b).sum() - (c @ d).sum())
+    abs_sum = iters * float((np.abs(a) @ np.abs(b)).sum() + (np.abs(c) @ np.abs(d)).sum())
+    return checksum, abs_sum
+
+
+def burn_checksum(nonce: int, iters: int):
+    """(checksum, abs_sum) in float64: iters*(sum(A.B) - sum(C.D)) and
+    iters*(sum(|A|.|B|) + sum(|C|.|D|))."""
+    return _burn_sums(*burn_operands(nonce), iters)
+
+
+def burn_bound(iters: int, abs_sum: float) -> float:
+    """Any-order fp32 summation bound: every product passes through at most
+    16*iters + 22 roundings (16 per MFMA over k, iters accumulations, 16
+    registers, 6 cross-lane folds, with slack), each at most 2^-23 relative
+    whether the unit truncates or rounds to nearest."""
+    return (16 * iters + 22) * 2.0 ** -23 * abs_sum
+
+
+BURN_MARGIN = 4      # for the MFMA's unspecified internal alignment
+
+
+def wrong_burn_models(nonce: int, iters: int) -> dict:
+    a, b, c, d = burn_operands(nonce)
+    rev = np.r_[7:-1:-1, 15:7:-1]     # element j <-> 7-j within each lane's fragment
+    swp = np.r_[8:16, 0:8]            # the two half-waves' k blocks exchanged
+    return {
+        "b_fragment_reversed": _burn_sums(a, b[rev, :], c, d[rev, :], iters)[0],
+        "half_wave_k_blocks_swapped": _burn_sums(a[:, swp], b, c[:, swp], d, iters)[0],
+        "iters_plus_1": _burn_sums(a, b, c, d, iters + 1)[0],
+    }
+
+
+# ---- comparisons on raw kernel outputs ------------------------------------------
+def _bits(x) -> np.ndarray:
+    return np.ascontiguousarray(x).view(np.uint32)
+
+
+def assert_bit_equal(got, want, what: str) -> None:
+    got, want = _bits(np.asarray(got)).ravel(), _bits(np.asarray(want)).ravel()
+    assert got.shape == want.shape, f"{what}: {got.shape} words, want {want.shape}"
+    diff = np.flatnonzero(got != want)
+    assert diff.size == 0, (f"{what}: {diff.size}/{got.size} words differ, first at {int(diff[0])}: "
+                            f"got {int(got[diff[0]]):#010x}, want {int(want[diff[0]]):#010x}")
+
+
+def check_canaries(canaries: dict, fill: int) -> None:
+    """Every guard byte before and after every buffer still holds `fill`."""
+    assert canaries, "no canaries recorded"
+    for name, arr in canaries.items():
+        hit = np.flatnonzero(np.asarray(arr).ravel() != fill)
+        assert hit.size == 0, f"{name}: {hit.size} guard bytes overwritten, first at offset {int(hit[0])}"
+
+
+def check_liveness(out, scratch, meta, nonce: int, iters: int) -> None:
+    want = tile_f32(nonce, iters)
+    assert_bit_equal(out, want, "out")
+    assert_bit_equal(scratch, scratch_image(want), "scratch")
+    meta = np.asarray(meta, dtype=np.uint32)
+    assert meta.shape == (4,)
+    assert int(meta[META_MAGIC]) == PROBE_MAGIC, f"meta magic {int(meta[META_MAGIC]):#x}"
+    assert int(meta[META_NONCE]) == nonce, f"meta nonce {int(meta[META_NONCE])}, want {nonce}"
+    assert int(meta[META_XCC]) < NUM_XCC_MAX, f"meta xcc {int(meta[META_XCC])}"
+
+
+def check_sweep(records, tiles, nonce: int, iters: int, grid: int) -> None:
+    records = np.asarray(records, dtype=np.uint32).reshape(grid, REC_WORDS)
+    tiles = np.asarray(tiles, dtype=np.float32).reshape(grid, PROBE_M, PROBE_N)
+    for wg in range(grid):
+        rec = [int(x) for x in records[wg]]
+        assert rec[REC_MAGIC] == SWEEP_MAGIC, f"wg {wg}: magic {rec[REC_MAGIC]:#x}"
+        assert rec[REC_WG] == wg, f"wg {wg}: record says wg {rec[REC_WG]}"
+        assert rec[REC_NONCE] == nonce ^ wg, f"wg {wg}: nonce word {rec[REC_NONCE]:#x}"
+        assert rec[REC_MFMA_BAD] == 0, f"wg {wg}: mfma_bad {rec[REC_MFMA_BAD]}"
+        assert rec[REC_LDS_BAD] == 0, f"wg {wg}: lds_bad {rec[REC_LDS_BAD]}"
+        assert 1 <= rec[REC_ARRIVED] <= grid, f"wg {wg}: arrived {rec[REC_ARRIVED]}"
+        t0 = rec[REC_T0_LO] | rec[REC_T0_HI] << 32
+        t1 = rec[REC_T1_LO] | rec[REC_T1_HI] << 32
+        assert t1 >= t0, f"wg {wg}: t1 {t1} < t0 {t0}"
+        assert rec[REC_XCC] < NUM_XCC_MAX, f"wg {wg}: xcc {rec[REC_XCC]}"
+        assert_bit_equal(tiles[wg], tile_f32(sweep_nonce(nonce, wg, 0), iters), f"wg {wg} tile")
+
+
+def hbm_fill_image(n16: int, seed: int, poison_unit=None) -> np.ndarray:
+    """What mi355x_hbm_fill must leave in the buffer (uint32 words)."""
+    want = hbm_pattern_words(4 * n16, seed)
+    if poison_unit is not None and poison_unit < n16:
+        want[4 * poison_unit] ^= np.uint32(M32)
+    return want
+
+
+def check_hbm_fill(buf, n16: int, seed: int, poison_unit=None) -> None:
+    assert_bit_equal(np.asarray(buf, dtype=np.uint32), hbm_fill_image(n16, seed, poison_unit), "buf")
+
+
+def check_hbm_check(bad, first_bad, corrupt) -> None:
+    """`corrupt`: the (unit, word) pairs the host corrupted. `bad` must count
+    exactly those words and `first_bad` name the lowest such unit (all ones if none)."""
+    words = {(int(u), int(w)) for u, w in corrupt}
+    want_first = min((u for u, _ in words), default=M64)
+    assert int(np.asarray(bad).ravel()[0]) == len(words), f"bad {int(np.asarray(bad).ravel()[0])}, want {len(words)}"
+    got_first = int(np.asarray(first_bad).ravel()[0])
+    assert got_first == want_first, f"first_bad {got_first:#x}, want {want_first:#x}"
+
+
+def check_burn(records, counters_host, counters, nonce: int, iters: int, grid: int) -> float:
+    """Asserts the burn records and returns |gpu - ref| / bound of the checksum."""
+    records = np.asarray(records, dtype=np.uint32).reshape(grid, REC_WORDS)
+    for wg in range(grid):
+        rec = [int(x) for x in records[wg]]
+        assert rec[PREC_MAGIC] == PERF_MAGIC, f"wg {wg}: magic {rec[PREC_MAGIC]:#x}"
+        assert rec[PREC_WG] == wg, f"wg {wg}: record says wg {rec[PREC_WG]}"
+        assert rec[PREC_NONCE] == nonce ^ wg, f"wg {wg}: nonce word {rec[PREC_NONCE]:#x}"
+        rt0 = rec[PREC_RT0_LO] | rec[PREC_RT0_HI] << 32
+        rt1 = rec[PREC_RT1_LO] | rec[PREC_RT1_HI] << 32
+        assert rt1 >= rt0, f"wg {wg}: rt1 {rt1} < rt0 {rt0}"
+        assert rec[PREC_CYC_LO] | rec[PREC_CYC_HI] << 32 > 0, f"wg {wg}: no shader clock ticks"
+        assert rec[PREC_XCC] < NUM_XCC_MAX, f"wg {wg}: xcc {rec[PREC_XCC]}"
+    assert_bit_equal(np.asarray(counters_host, dtype=np.uint32), np.asarray(counters, dtype=np.uint32),
+                     "hbm_counters_host")
+    sums = np.ascontiguousarray(records[:, PREC_SUM:PREC_SUM + 4]).ravel()
+    assert (sums == sums[0]).all(), f"checksums differ between waves: {[hex(int(s)) for s in sums]}"
+    ratio = burn_ratio(records, nonce, iters)
+    assert ratio <= BURN_MARGIN, (f"checksum {burn_gpu_checksum(records)!r} vs reference "
+                                  f"{burn_checksum(nonce, iters)[0]!r}: |diff| is {ratio:.3f} x bound, "
+                                  f"allowed {BURN_MARGIN}")   # a NaN ratio fails too
+    return ratio
+
+
+def burn_gpu_checksum(records) -> float:
+    """Workgroup 0 wave 0's checksum word as a float."""
+    words = np.asarray(records, dtype=np.uint32).ravel()[PREC_SUM:PREC_SUM + 1].copy()
+    return float(words.view(np.float32)[0])
+
+
+def burn_ratio(records, nonce: int, iters: int) -> float:
+    """|gpu - ref| / bound for the checksum in `records`."""
+    ref, abs_sum = burn_checksum(nonce, iters)
+    return abs(burn_gpu_checksum(records) - ref) / burn_bound(iters, abs_sum)

@@ -1,0 +1,230 @@
+"""Raw launcher for the kernels of liveness_gfx950.hsaco: every byte a kernel
+wrote, saved as .npy, with guard regions around every buffer.
+
+    python -m rocm_k8s_device_plugin_amd.testing.raw_kernels REQUESTS.json OUTDIR
+
+REQUESTS.json is a list of requests, run in order:
+
+    {"id": ..., "kernel": "liveness", "nonce": n, "iters": k}
+    {"id": ..., "kernel": "sweep", "nonce": n, "iters": k, "grid": g, "wait_ticks": t}
+    {"id": ..., "kernel": "hbm_fill", "n16": u, "grid": g, "threads": t, "seed": s, "poison_unit": p | null}
+    {"id": ..., "kernel": "hbm_check", "n16": u, "grid": g, "threads": t, "seed": s, "buf_npy": file}
+    {"id": ..., "kernel": "burn", "nonce": n, "iters": k, "grid": g, "hbm_counters": [4 words]}
+
+For each request OUTDIR gets <id>.<buffer>.npy and <id>.<buffer>.canary.npy
+(2 x CANARY_BYTES: the guard before and after the buffer), and OUTDIR/status.json
+names the completed requests and the first error. The launcher stops at the
+first HIP error, or at any non-success from the synchronize after a kernel,
+writes what it has, and exits non-zero; it never retries.
+
+A ctypes wrapper over one libamdhip64: the ROCm installation's, which the
+project's own binaries link. torch brings a second HIP/ROCr pair, so this
+module must run in a process that has not imported torch. Kernel arguments are
+packed by ctypes.Structure mirrors of the structs in liveness_kernel.h (the
+kernels use explicit arguments only), and passed as one kernarg buffer.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import os
+import sys
+from pathlib import Path
+
+import numpy as np
+
+CANARY_BYTES = 4096
+CANARY_FILL = 0xA5
+OUT_PREFILL = 0xFF
+
+_u32, _i32, _u64, _ptr = ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64
+
+
+class LivenessArgs(ctypes.Structure):
+    _fields_ = [("out", _ptr), ("meta", _ptr), ("scratch", _ptr), ("nonce", _u32), ("iters", _i32)]
+
+
+class SweepArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("arrive", _ptr), ("nonce", _u32), ("iters", _i32),
+                ("grid", _u32), ("wait_ticks", _u32)]
+
+
+class HbmArgs(ctypes.Structure):
+    _fields_ = [("buf", _ptr), ("n16", _u64), ("bad", _ptr), ("first_bad", _ptr), ("threads", _u64),
+                ("poison_unit", _u64), ("seed", _u32), ("pad", _u32)]
+
+
+class BurnArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("hbm_counters", _ptr), ("hbm_counters_host", _ptr), ("nonce", _u32),
+                ("iters", _i32)]
+
+
+ARG_STRUCTS = {"mi355x_liveness_args": LivenessArgs, "mi355x_sweep_args": SweepArgs,
+               "mi355x_hbm_args": HbmArgs, "mi355x_burn_args": BurnArgs}
+
+# kernel -> (symbol, lanes per workgroup)
+KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_sweep", 256),
+           "hbm_fill": ("mi355x_hbm_fill", 256), "hbm_check": ("mi355x_hbm_check", 256),
+           "burn": ("mi355x_mfma_burn", 256)}
+
+_H2D, _D2H = 1, 2
+_LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
+
+
+def hip_library_path() -> str:
+    return os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")
+
+
+class HipError(RuntimeError):
+    pass
+
+
+class Hip:
+    def __init__(self):
+        if "torch" in sys.modules:
+            raise RuntimeError("raw_kernels must not share a process with torch (a second HIP runtime)")
+        self.lib = ctypes.CDLL(hip_library_path())
+        self.lib.hipGetErrorString.restype = ctypes.c_char_p
+        self.lib.hipGetErrorString.argtypes = [ctypes.c_int]
+        self.lib.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        self.lib.hipFree.argtypes = [ctypes.c_void_p]
+        self.lib.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        self.lib.hipModuleLoad.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p]
+        self.lib.hipModuleGetFunction.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_char_p]
+        self.lib.hipModuleLaunchKernel.argtypes = [ctypes.c_void_p] + [ctypes.c_uint] * 7 + [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+
+    def check(self, what: str, status: int) -> None:
+        if status != 0:
+            raise HipError(f"{what}: hipError {status}: {self.lib.hipGetErrorString(status).decode(errors='replace')}")
+
+    def call(self, name: str, *args) -> None:
+        self.check(name, getattr(self.lib, name)(*args))
+
+
+class Buffer:
+    """`initial` bytes of device memory between two CANARY_BYTES guard regions."""
+
+    def __init__(self, hip: Hip, name: str, dtype, initial: bytes):
+        assert len(initial) % 4 == 0 and len(initial) > 0
+        self.hip, self.name, self.dtype, self.nbytes = hip, name, np.dtype(dtype), len(initial)
+        guard = bytes([CANARY_FILL]) * CANARY_BYTES
+        image = guard + initial + guard
+        base = ctypes.c_void_p()
+        hip.call("hipMalloc", ctypes.byref(base), len(image))
+        self.base = base.value
+        self.ptr = self.base + CANARY_BYTES
+        hip.call("hipMemcpy", self.base, image, len(image), _H2D)
+
+    def read(self):
+        """(content, canaries) as they are on the device now."""
+        host = ctypes.create_string_buffer(self.nbytes + 2 * CANARY_BYTES)
+        self.hip.call("hipMemcpy", host, self.base, len(host), _D2H)
+        raw = np.frombuffer(host.raw, dtype=np.uint8)
+        data = raw[CANARY_BYTES:CANARY_BYTES + self.nbytes].copy().view(self.dtype)
+        return data, np.stack([raw[:CANARY_BYTES], raw[CANARY_BYTES + self.nbytes:]])
+
+    def free(self):
+        self.hip.call("hipFree", self.base)
+
+
+def _filled(nbytes: int, byte: int) -> bytes:
+    return bytes([byte]) * nbytes
+
+
+def plan(req: dict, base_dir: Path):
+    """(buffer specs [(name, dtype, initial bytes)], args builder, workgroups) of a request."""
+    k = req["kernel"]
+    if k == "liveness":
+        bufs = [("out", np.float32, _filled(32 * 32 * 4, OUT_PREFILL)), ("meta", np.uint32, _filled(16, 0)),
+                ("scratch", np.float32, _filled(16 * 64 * 4, OUT_PREFILL))]
+        return bufs, lambda p: LivenessArgs(p["out"], p["meta"], p["scratch"], req["nonce"], req["iters"]), 1
+    if k == "sweep":
+        g = int(req["grid"])
+        bufs = [("records", np.uint32, _filled(g * 16 * 4, 0)), ("tiles", np.float32, _filled(g * 32 * 32 * 4, OUT_PREFILL)),
+                ("arrive", np.uint32, _filled(4, 0))]
+        return bufs, lambda p: SweepArgs(p["records"], p["tiles"], p["arrive"], req["nonce"], req["iters"], g,
+                                         req["wait_ticks"]), g
+    if k in ("hbm_fill", "hbm_check"):
+        n16 = int(req["n16"])
+        if k == "hbm_fill":
+            content = _filled(n16 * 16, 0x5A)
+            poison = req.get("poison_unit")
+            poison = 0xFFFFFFFFFFFFFFFF if poison is None else int(poison)
+        else:
+            path = Path(req["buf_npy"])
+            arr = np.load(path if path.is_absolute() else base_dir / path)
+            assert arr.dtype == np.uint32 and arr.size == 4 * n16, (arr.dtype, arr.size, n16)
+            content = arr.tobytes()
+            poison = 0xFFFFFFFFFFFFFFFF
+        bufs = [("buf", np.uint32, content), ("bad", np.uint32, _filled(4, 0)),
+                ("first_bad", np.uint64, _filled(8, 0xFF))]
+        return bufs, lambda p: HbmArgs(p["buf"], n16, p["bad"], p["first_bad"], int(req["threads"]), poison,
+                                       req["seed"], 0), int(req["grid"])
+    if k == "burn":
+        g = int(req["grid"])
+        counters = np.asarray(req["hbm_counters"], dtype=np.uint32)
+        assert counters.size == 4
+        bufs = [("records", np.uint32, _filled(g * 16 * 4, 0)), ("hbm_counters", np.uint32, counters.tobytes()),
+                ("hbm_counters_host", np.uint32, _filled(16, 0))]
+        return bufs, lambda p: BurnArgs(p["records"], p["hbm_counters"], p["hbm_counters_host"], req["nonce"],
+                                        req["iters"]), g
+    raise ValueError(f"unknown kernel {k!r}")
+
+
+def run_request(hip: Hip, functions: dict, req: dict, base_dir: Path, outdir: Path) -> None:
+    specs, make_args, wgs = plan(req, base_dir)
+    symbol, lanes = KERNELS[req["kernel"]]
+    bufs = [Buffer(hip, name, dtype, initial) for name, dtype, initial in specs]
+    args = make_args({b.name: b.ptr for b in bufs})
+    size = ctypes.c_size_t(ctypes.sizeof(args))
+    extra = (ctypes.c_void_p * 5)(_LAUNCH_PARAM_BUFFER_POINTER, ctypes.addressof(args), _LAUNCH_PARAM_BUFFER_SIZE,
+                                  ctypes.addressof(size), _LAUNCH_PARAM_END)
+    hip.call("hipModuleLaunchKernel", functions[symbol], wgs, 1, 1, lanes, 1, 1, 0, None, None, extra)
+    hip.call("hipDeviceSynchronize")
+    for b in bufs:
+        data, canary = b.read()
+        np.save(outdir / f"{req['id']}.{b.name}.npy", data)
+        np.save(outdir / f"{req['id']}.{b.name}.canary.npy", canary)
+    for b in bufs:
+        b.free()
+
+
+def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else argv
+    if len(argv) != 2:
+        print(__doc__, file=sys.stderr)
+        return 2
+    req_path, outdir = Path(argv[0]).resolve(), Path(argv[1])
+    requests = json.loads(req_path.read_text())
+    outdir.mkdir(parents=True, exist_ok=True)
+    status = {"completed": [], "error": None, "failed": None, "hip_library": hip_library_path()}
+    current = None
+    try:
+        from rocm_k8s_device_plugin_amd import _build
+        hip = Hip()
+        hip.call("hipInit", 0)
+        hip.call("hipSetDevice", int(os.environ.get("MI355X_RAW_DEVICE", "0")))
+        module = ctypes.c_void_p()
+        hip.call("hipModuleLoad", ctypes.byref(module), str(_build.HSACO).encode())
+        functions = {}
+        for symbol, _ in KERNELS.values():
+            f = ctypes.c_void_p()
+            hip.call("hipModuleGetFunction", ctypes.byref(f), module, symbol.encode())
+            functions[symbol] = f
+        for req in requests:
+            current = req["id"]
+            run_request(hip, functions, req, req_path.parent, outdir)
+            status["completed"].append(current)
+        current = None
+    except Exception as e:  # noqa: BLE001 - the first error ends the run, whatever it is
+        status["error"], status["failed"] = f"{type(e).__name__}: {e}", current
+    (outdir / "status.json").write_text(json.dumps(status, indent=1))
+    if status["error"]:
+        print(f"raw_kernels: stopped at {status['failed'] or 'start-up'}: {status['error']}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
