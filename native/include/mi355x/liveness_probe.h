@@ -128,6 +128,7 @@ int mi355x_hsa_peer_probe(int src, int dst, uint32_t nonce, uint64_t bytes, int 
 typedef struct {
   int ordinal;
   int ok;                 // every record present and correct, every tile exact, all XCDs seen
+                          // (XCDs are not counted against num_xcc when the agent reports none)
   int hsa_error;
   uint32_t nonce;
   int iters;
@@ -135,15 +136,16 @@ typedef struct {
   int cu_count;           // HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT
   int num_xcc;            // HSA_AMD_AGENT_INFO_NUM_XCC
   int records_ok;         // workgroups whose record is present, echoed the nonce and found no fault
-  uint32_t mfma_bad;      // MFMA elements differing from the VALU recomputation (all waves)
+  uint32_t mfma_bad;      // MFMA elements differing from the VALU recomputation (all waves; like
+                          // every count below, over present records only)
   uint32_t lds_bad;       // LDS words read back wrong
   uint32_t tile_bad;      // wave-0 tile elements differing from the host reference
   int cus_covered;        // distinct (XCC, SE, SH, CU) that ran a workgroup
   int xccs_covered;
-  int all_resident;       // every workgroup saw the whole grid resident before working
+  int all_resident;       // every record ok and every workgroup saw the whole grid resident before working
   int wgs_per_xcc[16];
   double kernel_us;       // dispatch start -> end (HSA profiling)
-  double arrival_spread_us;  // first to last workgroup arrival (s_memrealtime)
+  double arrival_spread_us;  // first to last workgroup arrival (s_memrealtime), present records
   double total_us;
   // > 0: an earlier sweep on this device has not completed for this long; its
   // queue and buffers stay allocated and no new sweep is submitted (at most one
@@ -164,7 +166,8 @@ int mi355x_hsa_chip_sweep(int ordinal, uint32_t nonce, int iters, double timeout
 // checksum must be bit-identical (same operands everywhere).
 typedef struct {
   int ordinal;
-  int ok;                    // pattern exact, checksums identical, every record present, all XCDs ran
+  int ok;                    // pattern exact, checksums identical and finite, every record present, all XCDs
+                             // ran (not counted against num_xcc when the agent reports none)
   int hsa_error;
   uint32_t nonce;
   uint64_t bytes;
@@ -174,21 +177,23 @@ typedef struct {
   double check_us;           // first read pass (right after the fill)
   double check2_us;          // second read pass
   double hbm_write_gbps;
-  double hbm_read_gbps;      // from the faster read pass
+  double hbm_read_gbps;      // from the faster read pass that has a time
   uint64_t hbm_bad_words;    // 32-bit words read back wrong (the pass that found more)
   uint64_t hbm_bad_words_pass2;
-  int64_t hbm_first_bad;     // lowest failing 16-byte unit, -1 if none
+  int64_t hbm_first_bad;     // lowest failing 16-byte unit, -1 if none (also when the counter names no unit
+                             // of the buffer: the kernels never wrote it, `error` says so)
   int mfma_iters;            // MFMA pairs per wave
   int mfma_grid;             // workgroups (MI355X_BURN_WGS_PER_CU per CU)
   int mfma_records_ok;
-  int mfma_checksum_mismatch;  // waves whose checksum differs from workgroup 0 wave 0
+  int mfma_checksum_mismatch;  // waves whose checksum word differs from wave 0 of the first present record;
+                               // every wave when that word is NaN or Inf (a correct checksum is finite)
   int mfma_xccs;             // distinct XCDs that ran burn workgroups
   double mfma_us;
   double mfma_tflops;        // dense bf16, from the dispatch time
   double clock_mhz_min;      // per-workgroup shader clock during the MFMA loop
-  double clock_mhz_median;
+  double clock_mhz_median;   // medians here are the upper one: sorted[n / 2]
   double clock_mhz_max;
-  double xcd_clock_mhz[16];  // median per XCD (0 = no workgroup seen)
+  double xcd_clock_mhz[16];  // median per XCD (0 = no workgroup with a measurable interval seen)
   double total_us;
   double in_flight_s;        // > 0: an earlier sweep / check on this device has not completed
   int kept_queue;            // ran on the device's kept probe queue (--serve --keep)

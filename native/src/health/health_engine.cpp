@@ -8,6 +8,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <utility>
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -842,17 +843,21 @@ std::vector<std::string> Engine::perf_problems(const ProbeOutcome& o) const {
       out.push_back(b);
     }
   }
-  std::vector<double> clocks;
-  for (double c : o.xcd_clock_mhz)
-    if (c > 0) clocks.push_back(c);
+  // XCDs that reported a clock, each with its id (an absent XCD reports 0)
+  std::vector<std::pair<size_t, double>> clocks;
+  for (size_t x = 0; x < o.xcd_clock_mhz.size(); ++x)
+    if (o.xcd_clock_mhz[x] > 0) clocks.emplace_back(x, o.xcd_clock_mhz[x]);
   if (clocks.size() >= 2 && cfg_.perf_min_xcd_clock_ratio > 0) {
-    std::vector<double> sorted = clocks;
+    std::vector<double> sorted;
+    for (const auto& c : clocks) sorted.push_back(c.second);
     std::sort(sorted.begin(), sorted.end());
     const double med = sorted[sorted.size() / 2];
-    const size_t i = static_cast<size_t>(std::min_element(clocks.begin(), clocks.end()) - clocks.begin());
-    if (clocks[i] < cfg_.perf_min_xcd_clock_ratio * med) {
+    const auto slowest = *std::min_element(clocks.begin(), clocks.end(),
+                                           [](const auto& a, const auto& b) { return a.second < b.second; });
+    if (slowest.second < cfg_.perf_min_xcd_clock_ratio * med) {
       char b[128];
-      std::snprintf(b, sizeof(b), "XCD %zu at %.0f MHz vs median %.0f MHz under MFMA load", i, clocks[i], med);
+      std::snprintf(b, sizeof(b), "XCD %zu at %.0f MHz vs median %.0f MHz under MFMA load", slowest.first,
+                    slowest.second, med);
       out.push_back(b);
     }
   }

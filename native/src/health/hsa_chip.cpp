@@ -17,6 +17,7 @@
 #include <utility>
 #include <vector>
 
+#include "chip_verify.h"
 #include "hsa_runtime.h"
 #include "probe_verify.h"
 
@@ -122,12 +123,6 @@ double dispatch_us(const Agent& ag, hsa_signal_t sig) {
   hsa_amd_profiling_dispatch_time_t dt{};
   if (H().hsa_amd_profiling_get_dispatch_time(ag.agent, sig, &dt) != HSA_STATUS_SUCCESS || !g_rt.ts_freq) return 0;
   return static_cast<double>(dt.end - dt.start) * 1e6 / static_cast<double>(g_rt.ts_freq);
-}
-
-double median_of(std::vector<double> v) {
-  if (v.empty()) return 0;
-  std::sort(v.begin(), v.end());
-  return v[v.size() / 2];
 }
 
 struct KernelSym {
@@ -359,54 +354,7 @@ extern "C" int mi355x_hsa_chip_sweep(int ordinal, uint32_t nonce, int iters, dou
     return finish();
   }
   out->kernel_us = dispatch_us(ag, dw.sig->s);
-  {
-    std::vector<uint32_t> keys;
-    keys.reserve(grid);
-    uint64_t tmin = UINT64_MAX, tmax = 0;
-    uint32_t xmask = 0;
-    bool all_res = true;
-    std::vector<float> want(MI355X_PROBE_OUT);
-    for (uint32_t w = 0; w < grid; ++w) {
-      const uint32_t* r = records + static_cast<size_t>(w) * MI355X_SWEEP_REC_WORDS;
-      const bool present = r[MI355X_REC_MAGIC] == MI355X_SWEEP_MAGIC && r[MI355X_REC_WG] == w &&
-                           r[MI355X_REC_NONCE] == (nonce ^ w);
-      if (!present) continue;
-      out->mfma_bad += r[MI355X_REC_MFMA_BAD];
-      out->lds_bad += r[MI355X_REC_LDS_BAD];
-      const uint32_t x = r[MI355X_REC_XCC] & 0xF;
-      xmask |= 1u << x;
-      ++out->wgs_per_xcc[x];
-      keys.push_back((x << 16) | ((r[MI355X_REC_HWID] >> 8) & 0xFF));
-      all_res = all_res && r[MI355X_REC_ARRIVED] >= grid;
-      const uint64_t t = (static_cast<uint64_t>(r[MI355X_REC_T0_HI]) << 32) | r[MI355X_REC_T0_LO];
-      tmin = t < tmin ? t : tmin;
-      tmax = t > tmax ? t : tmax;
-      // wave 0's tile against the host reference
-      const uint32_t nw = sweep_nonce(nonce, w, 0);
-      uint32_t tb = 0;
-      const float* tile = tiles + static_cast<size_t>(w) * MI355X_PROBE_OUT;
-      for (int i = 0; i < MI355X_PROBE_M; ++i)
-        for (int j = 0; j < MI355X_PROBE_N; ++j) {
-          float dot = 0.f;
-          for (int k = 0; k < MI355X_PROBE_K; ++k) dot += probe_a(i, k, nw) * probe_b(k, j, nw);
-          const float e = probe_c(i, j, nw) + static_cast<float>(out->iters) * dot;
-          tb += !mi355x::same_bits(tile[i * MI355X_PROBE_N + j], e);
-        }
-      out->tile_bad += tb;
-      if (r[MI355X_REC_MFMA_BAD] == 0 && r[MI355X_REC_LDS_BAD] == 0 && tb == 0) ++out->records_ok;
-    }
-    std::sort(keys.begin(), keys.end());
-    out->cus_covered = static_cast<int>(std::unique(keys.begin(), keys.end()) - keys.begin());
-    out->xccs_covered = __builtin_popcount(xmask);
-    out->all_resident = all_res && out->records_ok == static_cast<int>(grid);
-    if (tmax >= tmin && tmin != UINT64_MAX) out->arrival_spread_us = static_cast<double>(tmax - tmin) / 100.0;
-    out->ok = out->records_ok == static_cast<int>(grid) &&
-              (out->num_xcc <= 0 || out->xccs_covered == out->num_xcc);
-    if (!out->ok)
-      std::snprintf(out->error, sizeof(out->error),
-                    "%d/%d workgroups correct (mfma_bad=%u lds_bad=%u tile_bad=%u), %d/%d XCDs ran", out->records_ok,
-                    grid, out->mfma_bad, out->lds_bad, out->tile_bad, out->xccs_covered, out->num_xcc);
-  }
+  mi355x::sweep_verdict(records, tiles, grid, out);
   free_bufs();
   return finish();
 }
@@ -521,7 +469,7 @@ extern "C" int mi355x_hsa_perf_check(int ordinal, uint32_t nonce, uint64_t bytes
   // counters: word 0 = 0 (bad words), words 2..3 = all ones (first bad unit)
   PERF_CHECK(H().hsa_amd_memory_fill(counters, 0u, 2), "zero counters");
   PERF_CHECK(H().hsa_amd_memory_fill(counters + 2, 0xFFFFFFFFu, 2), "init first-bad");
-  std::memset(h_counters, 0xA5, 16);   // overwritten by the burn kernel's copy
+  std::memset(h_counters, mi355x::kPerfCounterFillByte, 16);   // overwritten by the burn kernel's copy
   std::memset(records, 0, rec_bytes);
   std::memset(kargs, 0, 4 * kKernargBytes);
   {
@@ -561,63 +509,7 @@ extern "C" int mi355x_hsa_perf_check(int ordinal, uint32_t nonce, uint64_t bytes
   if (!wait_signal(w.sig->s, timeout_s)) return abandon("MFMA burn");
   out->mfma_us = dispatch_us(ag, w.sig->s);
 #undef PERF_CHECK
-  {
-    out->hbm_bad_words = h_counters[0] > h_counters[1] ? h_counters[0] : h_counters[1];
-    out->hbm_bad_words_pass2 = h_counters[1];
-    const uint64_t first = (static_cast<uint64_t>(h_counters[3]) << 32) | h_counters[2];
-    out->hbm_first_bad = first == ~0ull ? -1 : static_cast<int64_t>(first);
-    if (out->fill_us > 0) out->hbm_write_gbps = static_cast<double>(bytes) / (out->fill_us * 1e3);
-    const double best_check = out->check2_us > 0 && out->check2_us < out->check_us ? out->check2_us : out->check_us;
-    if (best_check > 0) out->hbm_read_gbps = static_cast<double>(bytes) / (best_check * 1e3);
-    const double flops = 2.0 * 32 * 32 * 16 * 2.0 * static_cast<double>(out->mfma_iters) *
-                         (MI355X_PERF_THREADS / 64) * static_cast<double>(burn_wgs);
-    if (out->mfma_us > 0) out->mfma_tflops = flops / (out->mfma_us * 1e6);
-    std::vector<double> clocks;
-    std::vector<std::vector<double>> per_xcd(16);
-    uint32_t ref = 0;
-    bool have_ref = false;
-    uint32_t xmask = 0;
-    for (uint32_t wg = 0; wg < burn_wgs; ++wg) {
-      const uint32_t* r = records + static_cast<size_t>(wg) * MI355X_PERF_REC_WORDS;
-      if (r[MI355X_PREC_MAGIC] != MI355X_PERF_MAGIC || r[MI355X_PREC_WG] != wg ||
-          r[MI355X_PREC_NONCE] != (nonce ^ wg))
-        continue;
-      ++out->mfma_records_ok;
-      for (int v = 0; v < MI355X_PERF_THREADS / 64; ++v) {
-        if (!have_ref) {
-          ref = r[MI355X_PREC_SUM + v];
-          have_ref = true;
-        } else if (r[MI355X_PREC_SUM + v] != ref) {
-          ++out->mfma_checksum_mismatch;
-        }
-      }
-      const uint64_t rt0 = (static_cast<uint64_t>(r[MI355X_PREC_RT0_HI]) << 32) | r[MI355X_PREC_RT0_LO];
-      const uint64_t rt1 = (static_cast<uint64_t>(r[MI355X_PREC_RT1_HI]) << 32) | r[MI355X_PREC_RT1_LO];
-      const uint64_t cyc = (static_cast<uint64_t>(r[MI355X_PREC_CYC_HI]) << 32) | r[MI355X_PREC_CYC_LO];
-      const uint32_t x = r[MI355X_PREC_XCC] & 0xF;
-      xmask |= 1u << x;
-      if (rt1 > rt0) {
-        const double mhz = static_cast<double>(cyc) / (static_cast<double>(rt1 - rt0) / 100.0);  // ticks per us
-        clocks.push_back(mhz);
-        per_xcd[x].push_back(mhz);
-      }
-    }
-    out->mfma_xccs = __builtin_popcount(xmask);
-    if (!clocks.empty()) {
-      out->clock_mhz_min = *std::min_element(clocks.begin(), clocks.end());
-      out->clock_mhz_max = *std::max_element(clocks.begin(), clocks.end());
-      out->clock_mhz_median = median_of(clocks);
-    }
-    for (int x = 0; x < 16; ++x) out->xcd_clock_mhz[x] = median_of(per_xcd[x]);
-    out->ok = out->hbm_bad_words == 0 && out->mfma_checksum_mismatch == 0 &&
-              out->mfma_records_ok == static_cast<int>(burn_wgs) &&
-              (out->num_xcc <= 0 || out->mfma_xccs == out->num_xcc);
-    if (!out->ok)
-      std::snprintf(out->error, sizeof(out->error),
-                    "hbm_bad_words=%llu first_bad_unit=%lld mfma records %d/%u checksum mismatches %d, %d/%d XCDs ran",
-                    static_cast<unsigned long long>(out->hbm_bad_words), static_cast<long long>(out->hbm_first_bad),
-                    out->mfma_records_ok, burn_wgs, out->mfma_checksum_mismatch, out->mfma_xccs, out->num_xcc);
-  }
+  mi355x::perf_verdict(records, h_counters, burn_wgs, out);
   free_bufs();
   return finish();
 }

@@ -1,7 +1,9 @@
-// Host-only view of the kernel contract in liveness_kernel.h and of
-// probe_verify.h::verify_tile, for tests/test_kernel_reference.py: the operand
-// generators at given indices, the layout of the four kernel-argument structs,
-// and verify_tile's verdict on tiles read from stdin. No HIP, no GPU.
+// Host-only view of the kernel contract in liveness_kernel.h, of
+// probe_verify.h::verify_tile and of the chip_verify.h verdicts, for
+// tests/test_kernel_reference.py and tests/test_verdict_reference.py: the
+// operand generators at given indices, the layout of the four kernel-argument
+// structs, and the host's verdict on tiles and records read from stdin, printed
+// as the probe prints it (probe_json.h). No HIP, no GPU.
 //
 //   kernel_contract_cli gen     < requests    one value per request line:
 //        a i k nonce | b k j nonce | c i j nonce | sweep_nonce nonce wg wave |
@@ -9,13 +11,30 @@
 //   kernel_contract_cli layout                "struct field offset" / "struct sizeof n" lines
 //   kernel_contract_cli verify  < records     one "ok mismatches error" line per binary record:
 //        uint32 nonce, int32 iters, 1024 floats, 4 meta words
+//   kernel_contract_cli sweep-verdict < cases  sweep_json lines of mi355x::sweep_verdict. A case:
+//        uint32 grid, nonce, int32 iters, num_xcc, uint32 variants; grid*16 record words; grid*1024 floats;
+//        then per variant: uint32 n and n patches (uint32 array, index, value), array 0 = records,
+//        1 = tiles as words. One line for the case as given, then one per variant: the case with
+//        that variant's words replaced (each variant starts from the case as given).
+//   kernel_contract_cli perf-verdict < cases   perf_json lines of mi355x::perf_verdict. A case:
+//        uint32 burn_wgs, nonce, int32 num_xcc, mfma_iters, uint64 bytes, double fill_us, check_us,
+//        check2_us, mfma_us, uint32 variants, pad; 4 counter words; burn_wgs*16 record words; variants
+//        as above, array 0 = records, 1 = counters.
+//   kernel_contract_cli json sweep|perf I U32 U64 I64 D ERRHEX
+//        the JSON of a result whose every int is I, uint32_t U32, uint64_t U64, int64_t I64, double D
+//        and whose error is the bytes ERRHEX names (at most 159)
 #include <cinttypes>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <cstdlib>
 #include <string>
+#include <utility>
+#include <vector>
 
+#include "chip_verify.h"
 #include "liveness_kernel.h"
+#include "probe_json.h"
 #include "probe_verify.h"
 
 static int cmd_gen() {
@@ -105,11 +124,189 @@ static int cmd_verify() {
   return 0;
 }
 
+static constexpr uint32_t kMaxWgs = 4096;   // mi355x_hsa_chip_sweep refuses more than 1024 CUs
+
+template <typename T>
+static bool read_n(T* dst, size_t n) {
+  return std::fread(dst, sizeof(T), n, stdin) == n;
+}
+
+struct Patch {
+  uint32_t array, index, value;
+};
+
+// One variant's patches applied to arrays[0] / arrays[1] (as 32-bit words of
+// the given lengths), `run` called, and the words put back.
+template <typename F>
+static bool with_variant(uint32_t* const arrays[2], const size_t lens[2], F run) {
+  uint32_t n = 0;
+  if (!read_n(&n, 1) || n > (1u << 24)) return false;
+  std::vector<Patch> patches(n);
+  if (n && !read_n(patches.data(), n)) return false;
+  std::vector<uint32_t> saved(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const Patch& p = patches[i];
+    if (p.array > 1 || p.index >= lens[p.array]) return false;
+    saved[i] = arrays[p.array][p.index];
+    arrays[p.array][p.index] = p.value;
+  }
+  run();
+  for (uint32_t i = n; i-- > 0;) arrays[patches[i].array][patches[i].index] = saved[i];
+  return true;
+}
+
+static int cmd_sweep_verdict() {
+  struct {
+    uint32_t grid, nonce;
+    int32_t iters, num_xcc;
+    uint32_t variants;
+  } h;
+  size_t got;
+  while ((got = std::fread(&h, 1, sizeof(h), stdin)) == sizeof(h)) {
+    if (h.grid == 0 || h.grid > kMaxWgs) {
+      std::fprintf(stderr, "sweep case: grid %u\n", h.grid);
+      return 2;
+    }
+    std::vector<uint32_t> records(static_cast<size_t>(h.grid) * MI355X_SWEEP_REC_WORDS);
+    std::vector<uint32_t> tiles(static_cast<size_t>(h.grid) * MI355X_PROBE_OUT);
+    if (!read_n(records.data(), records.size()) || !read_n(tiles.data(), tiles.size())) {
+      std::fprintf(stderr, "truncated sweep case\n");
+      return 2;
+    }
+    auto run = [&] {
+      mi355x_sweep_result r;
+      std::memset(&r, 0, sizeof(r));
+      r.nonce = h.nonce;
+      r.iters = h.iters;
+      r.num_xcc = h.num_xcc;
+      r.grid = static_cast<int>(h.grid);
+      std::vector<float> f(tiles.size());
+      std::memcpy(f.data(), tiles.data(), tiles.size() * sizeof(float));
+      mi355x::sweep_verdict(records.data(), f.data(), h.grid, &r);
+      std::printf("%s\n", mi355x::sweep_json(r).c_str());
+    };
+    run();
+    uint32_t* const arrays[2] = {records.data(), tiles.data()};
+    const size_t lens[2] = {records.size(), tiles.size()};
+    for (uint32_t v = 0; v < h.variants; ++v)
+      if (!with_variant(arrays, lens, run)) {
+        std::fprintf(stderr, "bad sweep variant %u\n", v);
+        return 2;
+      }
+  }
+  if (got != 0) {
+    std::fprintf(stderr, "truncated sweep header: %zu bytes\n", got);
+    return 2;
+  }
+  return 0;
+}
+
+static int cmd_perf_verdict() {
+  struct {
+    uint32_t burn_wgs, nonce;
+    int32_t num_xcc, mfma_iters;
+    uint64_t bytes;
+    double fill_us, check_us, check2_us, mfma_us;
+    uint32_t variants, pad;
+  } h;
+  static_assert(sizeof(h) == 64, "perf case header");
+  size_t got;
+  while ((got = std::fread(&h, 1, sizeof(h), stdin)) == sizeof(h)) {
+    if (h.burn_wgs == 0 || h.burn_wgs > kMaxWgs) {
+      std::fprintf(stderr, "perf case: burn_wgs %u\n", h.burn_wgs);
+      return 2;
+    }
+    std::vector<uint32_t> counters(4);
+    std::vector<uint32_t> records(static_cast<size_t>(h.burn_wgs) * MI355X_PERF_REC_WORDS);
+    if (!read_n(counters.data(), 4) || !read_n(records.data(), records.size())) {
+      std::fprintf(stderr, "truncated perf case\n");
+      return 2;
+    }
+    auto run = [&] {
+      mi355x_perf_result r;
+      std::memset(&r, 0, sizeof(r));
+      r.nonce = h.nonce;
+      r.bytes = h.bytes;
+      r.num_xcc = h.num_xcc;
+      r.mfma_iters = h.mfma_iters;
+      r.mfma_grid = static_cast<int>(h.burn_wgs);
+      r.fill_us = h.fill_us;
+      r.check_us = h.check_us;
+      r.check2_us = h.check2_us;
+      r.mfma_us = h.mfma_us;
+      mi355x::perf_verdict(records.data(), counters.data(), h.burn_wgs, &r);
+      std::printf("%s\n", mi355x::perf_json(r).c_str());
+    };
+    run();
+    uint32_t* const arrays[2] = {records.data(), counters.data()};
+    const size_t lens[2] = {records.size(), counters.size()};
+    for (uint32_t v = 0; v < h.variants; ++v)
+      if (!with_variant(arrays, lens, run)) {
+        std::fprintf(stderr, "bad perf variant %u\n", v);
+        return 2;
+      }
+  }
+  if (got != 0) {
+    std::fprintf(stderr, "truncated perf header: %zu bytes\n", got);
+    return 2;
+  }
+  return 0;
+}
+
+static void set_error(char (&dst)[160], const char* hex) {
+  size_t n = 0;
+  for (; hex[0] && hex[1] && n + 1 < sizeof(dst); hex += 2) {
+    const char b[3] = {hex[0], hex[1], 0};
+    dst[n++] = static_cast<char>(std::strtoul(b, nullptr, 16));
+  }
+  dst[n] = 0;
+}
+
+static int cmd_json(int argc, char** argv) {
+  if (argc != 9) return 2;
+  const std::string kind = argv[2];
+  const int i = static_cast<int>(std::strtoll(argv[3], nullptr, 0));
+  const uint32_t u = static_cast<uint32_t>(std::strtoull(argv[4], nullptr, 0));
+  const uint64_t u64 = std::strtoull(argv[5], nullptr, 0);
+  const int64_t i64 = std::strtoll(argv[6], nullptr, 0);
+  const double d = std::strtod(argv[7], nullptr);
+  if (kind == "sweep") {
+    mi355x_sweep_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.ordinal = r.ok = r.hsa_error = r.iters = r.grid = r.cu_count = r.num_xcc = r.records_ok = r.cus_covered =
+        r.xccs_covered = r.all_resident = r.kept_queue = i;
+    for (int& w : r.wgs_per_xcc) w = i;
+    r.nonce = r.mfma_bad = r.lds_bad = r.tile_bad = u;
+    r.kernel_us = r.arrival_spread_us = r.total_us = r.in_flight_s = d;
+    set_error(r.error, argv[8]);
+    std::printf("%s\n", mi355x::sweep_json(r).c_str());
+  } else if (kind == "perf") {
+    mi355x_perf_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.ordinal = r.ok = r.hsa_error = r.cu_count = r.num_xcc = r.mfma_iters = r.mfma_grid = r.mfma_records_ok =
+        r.mfma_checksum_mismatch = r.mfma_xccs = r.kept_queue = i;
+    r.nonce = u;
+    r.bytes = r.hbm_bad_words = r.hbm_bad_words_pass2 = u64;
+    r.hbm_first_bad = i64;
+    r.fill_us = r.check_us = r.check2_us = r.hbm_write_gbps = r.hbm_read_gbps = r.mfma_us = r.mfma_tflops =
+        r.clock_mhz_min = r.clock_mhz_median = r.clock_mhz_max = r.total_us = r.in_flight_s = d;
+    for (double& c : r.xcd_clock_mhz) c = d;
+    set_error(r.error, argv[8]);
+    std::printf("%s\n", mi355x::perf_json(r).c_str());
+  } else {
+    return 2;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const std::string cmd = argc > 1 ? argv[1] : "";
   if (cmd == "gen") return cmd_gen();
   if (cmd == "layout") return cmd_layout();
   if (cmd == "verify") return cmd_verify();
-  std::fprintf(stderr, "usage: %s gen|layout|verify\n", argv[0]);
+  if (cmd == "sweep-verdict") return cmd_sweep_verdict();
+  if (cmd == "perf-verdict") return cmd_perf_verdict();
+  if (cmd == "json") return cmd_json(argc, argv);
+  std::fprintf(stderr, "usage: %s gen|layout|verify|sweep-verdict|perf-verdict|json\n", argv[0]);
   return 2;
 }

@@ -7,6 +7,8 @@ Outputs land inside the package so they travel with the repo snapshot:
 * ``bin/mi355x-liveness-probe``   HSA-direct probe executable (health loop, bench "container")
 * ``bin/mi355x-liveness-probe-hip`` the same probe through the HIP runtime
 * ``kernels/liveness_gfx950.hsaco``
+* ``bin/kernel_contract_cli``     host-only driver of the kernel contract and the sweep /
+  throughput verdicts (testing/contract_cli.py)
 
 ``ensure_built()`` is cheap when everything is up to date (one ninja no-op).
 """
@@ -32,6 +34,7 @@ PROBE_EXE_HIP = PKG_DIR / "bin" / "mi355x-liveness-probe-hip"
 MOUNTEMU_EXE = PKG_DIR / "bin" / "mi355x-probe-mountemu"
 HIP_DEVEMU_EXE = PKG_DIR / "bin" / "mi355x-probe-hip-devemu"
 HSACO = PKG_DIR / "kernels" / "liveness_gfx950.hsaco"
+CONTRACT_CLI = PKG_DIR / "bin" / "kernel_contract_cli"
 
 
 def hipcc_available() -> bool:
@@ -204,7 +207,7 @@ def ensure_built(hip: bool | None = None) -> None:
         hip = hipcc_available()
     if hip in _checked:
         return
-    targets = [NATIVE_SO] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO] if hip else [])
+    targets = [NATIVE_SO, CONTRACT_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO] if hip else [])
     if not _up_to_date(targets, hip):
         BUILD_DIR.mkdir(parents=True, exist_ok=True)
         with open(BUILD_DIR.parent / ".build.lock", "w") as lk:

@@ -496,12 +496,13 @@ class HealthMonitor:
             v = float(d.get(key) or 0.0)
             if floor > 0 and v < floor * share:
                 out.append(f"{what} {v:.0f} {unit} < {floor * share:.0f}")
-        clocks = [float(x) for x in (d.get("xcd_clock_mhz") or []) if x and float(x) > 0]
+        # XCDs that reported a clock, each with its id (an absent XCD reports 0)
+        clocks = [(x, float(m)) for x, m in enumerate(d.get("xcd_clock_mhz") or []) if m and float(m) > 0]
         if len(clocks) >= 2 and c.perf_min_xcd_clock_ratio > 0:
-            med = sorted(clocks)[len(clocks) // 2]
-            i = min(range(len(clocks)), key=clocks.__getitem__)
-            if clocks[i] < c.perf_min_xcd_clock_ratio * med:
-                out.append(f"XCD {i} at {clocks[i]:.0f} MHz vs median {med:.0f} MHz under MFMA load")
+            med = sorted(mhz for _, mhz in clocks)[len(clocks) // 2]
+            xcd, slowest = min(clocks, key=lambda xc: xc[1])
+            if slowest < c.perf_min_xcd_clock_ratio * med:
+                out.append(f"XCD {xcd} at {slowest:.0f} MHz vs median {med:.0f} MHz under MFMA load")
         return out
 
     async def _perf_check(self, ords: Dict[str, int]) -> None:

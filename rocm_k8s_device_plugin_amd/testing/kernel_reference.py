@@ -297,3 +297,184 @@ def burn_ratio(records, nonce: int, iters: int) -> float:
     """|gpu - ref| / bound for the checksum in `records`."""
     ref, abs_sum = burn_checksum(nonce, iters)
     return abs(burn_gpu_checksum(records) - ref) / burn_bound(iters, abs_sum)
+
+
+# ---- what the host decides from the records (chip_verify.h) --------------------
+# Written from the field comments of mi355x_sweep_result / mi355x_perf_result
+# (liveness_probe.h) and the record words above, in Python ints: the keys are
+# the keys of the probe's JSON object, for the fields the records and the
+# caller's inputs determine (the rest -- ordinal, dispatch times -- belong to the
+# dispatch, not the verdict).
+SWEEP_FLOAT_DIGITS = {"arrival_spread_us": 2}
+PERF_FLOAT_DIGITS = {"fill_us": 1, "check_us": 1, "check2_us": 1, "mfma_us": 1, "hbm_write_gbps": 1,
+                     "hbm_read_gbps": 1, "mfma_tflops": 1, "clock_mhz_min": 0, "clock_mhz_median": 0,
+                     "clock_mhz_max": 0, "xcd_clock_mhz": 0}
+BURN_WAVES = 4
+MFMA_FLOPS = 2 * 32 * 32 * 16          # one v_mfma_f32_32x32x16
+REALTIME_MHZ = 100                     # s_memrealtime
+COUNTER_FILL_WORD = 0xA5A5A5A5         # the host counter words before the burn kernel's copy
+
+_sweep_tiles_cache: dict = {}
+
+
+def sweep_tiles(nonce: int, iters: int, grid: int) -> np.ndarray:
+    """Wave 0's tile of every workgroup, float32 (grid, 32, 32). Computed once
+    per (nonce, iters, grid) and read-only: copy before changing it."""
+    key = (nonce, iters, grid)
+    if key not in _sweep_tiles_cache:
+        t = np.stack([tile_f32(sweep_nonce(nonce, wg, 0), iters) for wg in range(grid)])
+        t.setflags(write=False)
+        _sweep_tiles_cache[key] = t
+    return _sweep_tiles_cache[key]
+
+
+def spread_placement(grid: int, xcds: int) -> list:
+    """(xcc, cu-bits) per workgroup: workgroups dealt round-robin to the XCDs,
+    each to the next CU of its XCD."""
+    return [(wg % xcds, wg // xcds) for wg in range(grid)]
+
+
+def healthy_sweep(grid: int, nonce: int, iters: int, placement):
+    """(records, tiles) a correct mi355x_chip_sweep would write: every
+    workgroup saw the whole grid, arrivals one tick apart."""
+    placement = list(placement)
+    assert len(placement) == grid
+    recs = np.zeros((grid, REC_WORDS), dtype=np.uint32)
+    for wg, (xcc, cu) in enumerate(placement):
+        t0 = 0x12_0000_0000 + wg
+        t1 = t0 + 5000
+        recs[wg, REC_MAGIC], recs[wg, REC_NONCE], recs[wg, REC_WG] = SWEEP_MAGIC, nonce ^ wg, wg
+        recs[wg, REC_XCC], recs[wg, REC_HWID], recs[wg, REC_ARRIVED] = xcc, (cu << 8) | 0x3, grid
+        recs[wg, REC_T0_LO], recs[wg, REC_T0_HI] = t0 & M32, t0 >> 32
+        recs[wg, REC_T1_LO], recs[wg, REC_T1_HI] = t1 & M32, t1 >> 32
+    return recs, sweep_tiles(nonce, iters, grid).copy()
+
+
+def _per_wg(value, grid: int) -> list:
+    return [int(value)] * grid if np.isscalar(value) else [int(v) for v in value]
+
+
+def healthy_burn(burn_wgs: int, nonce: int, placement, cyc, rt_ticks, checksum_word: int) -> np.ndarray:
+    """The records a correct mi355x_mfma_burn would write; `cyc` (shader clock
+    ticks) and `rt_ticks` (100 MHz ticks) over the loop, one value or one per
+    workgroup; every wave's checksum is `checksum_word`."""
+    placement = list(placement)
+    assert len(placement) == burn_wgs
+    cyc, rt_ticks = _per_wg(cyc, burn_wgs), _per_wg(rt_ticks, burn_wgs)
+    recs = np.zeros((burn_wgs, REC_WORDS), dtype=np.uint32)
+    for wg, (xcc, cu) in enumerate(placement):
+        rt0 = 0xFFFF_FF00 + 7 * wg                       # some intervals straddle 2^32
+        rt1 = rt0 + rt_ticks[wg]
+        recs[wg, PREC_MAGIC], recs[wg, PREC_WG], recs[wg, PREC_NONCE] = PERF_MAGIC, wg, nonce ^ wg
+        recs[wg, PREC_XCC], recs[wg, PREC_HWID] = xcc, (cu << 8) | 0x1
+        recs[wg, PREC_RT0_LO], recs[wg, PREC_RT0_HI] = rt0 & M32, rt0 >> 32
+        recs[wg, PREC_RT1_LO], recs[wg, PREC_RT1_HI] = rt1 & M32, rt1 >> 32
+        recs[wg, PREC_CYC_LO], recs[wg, PREC_CYC_HI] = cyc[wg] & M32, cyc[wg] >> 32
+        recs[wg, PREC_SUM:PREC_SUM + BURN_WAVES] = checksum_word
+    return recs
+
+
+def _xcd_entries(num_xcc: int) -> int:
+    """How many per-XCD entries the JSON carries: the agent's XCDs, 8 when it named none."""
+    return min(16, num_xcc if num_xcc > 0 else NUM_XCC_MAX)
+
+
+def _median(values) -> float:
+    return sorted(values)[len(values) // 2] if values else 0.0
+
+
+def sweep_verdict(records, tiles, grid: int, nonce: int, iters: int, num_xcc: int) -> dict:
+    rec = np.asarray(records, dtype=np.uint32).reshape(grid, REC_WORDS).astype(np.uint64)
+    got = _bits(np.asarray(tiles, dtype=np.float32)).reshape(grid, PROBE_M * PROBE_N)
+    want = _bits(sweep_tiles(nonce, iters, grid)).reshape(grid, PROBE_M * PROBE_N)
+    wrong = (got != want).sum(axis=1)
+    wgs = np.arange(grid, dtype=np.uint64)
+    present = ((rec[:, REC_MAGIC] == SWEEP_MAGIC) & (rec[:, REC_WG] == wgs)
+               & (rec[:, REC_NONCE] == (np.uint64(nonce) ^ wgs)))
+    good = present & (rec[:, REC_MFMA_BAD] == 0) & (rec[:, REC_LDS_BAD] == 0) & (wrong == 0)
+    seen = rec[present]                                    # absent records count for nothing
+    xccs = [int(x) & 0xF for x in seen[:, REC_XCC]]
+    cus = [int(h) >> 8 & 0xFF for h in seen[:, REC_HWID]]
+    arrivals = [int(lo) | int(hi) << 32 for lo, hi in zip(seen[:, REC_T0_LO], seen[:, REC_T0_HI])]
+    records_ok = int(good.sum())
+    out = {
+        "nonce": nonce, "iters": iters, "grid": grid, "num_xcc": num_xcc,
+        "records_ok": records_ok,
+        "mfma_bad": sum(int(x) for x in seen[:, REC_MFMA_BAD]) & M32,      # a uint32_t field
+        "lds_bad": sum(int(x) for x in seen[:, REC_LDS_BAD]) & M32,
+        "tile_bad": int(wrong[present].sum()),
+        "cus_covered": len(set(zip(xccs, cus))),
+        "xccs_covered": len(set(xccs)),
+        "all_resident": records_ok == grid and all(int(a) >= grid for a in seen[:, REC_ARRIVED]),
+        "wgs_per_xcc": [xccs.count(x) for x in range(_xcd_entries(num_xcc))],
+        "arrival_spread_us": (max(arrivals) - min(arrivals)) / REALTIME_MHZ if arrivals else 0.0,
+    }
+    out["ok"] = records_ok == grid and (num_xcc <= 0 or out["xccs_covered"] == num_xcc)
+    return out
+
+
+def _finite_f32_word(word: int) -> bool:
+    return word >> 23 & 0xFF != 0xFF
+
+
+def perf_verdict(records, counters, burn_wgs: int, nonce: int, num_xcc: int, bytes: int, mfma_iters: int,  # noqa: A002
+                 fill_us: float, check_us: float, check2_us: float, mfma_us: float) -> dict:
+    recs = [[int(x) for x in row] for row in np.asarray(records, dtype=np.uint32).reshape(burn_wgs, REC_WORDS)]
+    pass1, pass2, first_lo, first_hi = (int(x) for x in np.asarray(counters, dtype=np.uint32).ravel())
+    first = first_lo | first_hi << 32
+    present = [wg for wg, r in enumerate(recs)
+               if r[PREC_MAGIC] == PERF_MAGIC and r[PREC_WG] == wg and r[PREC_NONCE] == nonce ^ wg]
+    sums = [recs[wg][PREC_SUM + v] for wg in present for v in range(BURN_WAVES)]
+    if sums and _finite_f32_word(sums[0]):
+        mismatch = sum(1 for s in sums if s != sums[0])
+    else:
+        mismatch = len(sums)              # a NaN / Inf checksum agrees with nothing, itself included
+    clocks, per_xcd = [], [[] for _ in range(16)]
+    for wg in present:
+        r = recs[wg]
+        ticks = (r[PREC_RT1_LO] | r[PREC_RT1_HI] << 32) - (r[PREC_RT0_LO] | r[PREC_RT0_HI] << 32)
+        if ticks > 0:
+            mhz = (r[PREC_CYC_LO] | r[PREC_CYC_HI] << 32) / (ticks / REALTIME_MHZ)
+            clocks.append(mhz)
+            per_xcd[r[PREC_XCC] & 0xF].append(mhz)
+    reads = [t for t in (check_us, check2_us) if t > 0]
+    flops = MFMA_FLOPS * 2 * mfma_iters * BURN_WAVES * burn_wgs
+    xccs = {recs[wg][PREC_XCC] & 0xF for wg in present}
+    out = {
+        "nonce": nonce, "bytes": bytes, "num_xcc": num_xcc, "mfma_iters": mfma_iters, "mfma_grid": burn_wgs,
+        "fill_us": fill_us, "check_us": check_us, "check2_us": check2_us, "mfma_us": mfma_us,
+        "hbm_write_gbps": bytes / (fill_us * 1e3) if fill_us > 0 else 0.0,
+        "hbm_read_gbps": bytes / (min(reads) * 1e3) if reads else 0.0,
+        "hbm_bad_words": max(pass1, pass2), "hbm_bad_words_pass2": pass2,
+        "hbm_first_bad": first if first < bytes // 16 else -1,
+        "mfma_records_ok": len(present), "mfma_checksum_mismatch": mismatch, "mfma_xccs": len(xccs),
+        "mfma_tflops": flops / (mfma_us * 1e6) if mfma_us > 0 else 0.0,
+        "clock_mhz_min": min(clocks, default=0.0), "clock_mhz_median": _median(clocks),
+        "clock_mhz_max": max(clocks, default=0.0),
+        "xcd_clock_mhz": [_median(c) for c in per_xcd][:_xcd_entries(num_xcc)],
+    }
+    out["ok"] = (out["hbm_bad_words"] == 0 and mismatch == 0 and len(present) == burn_wgs
+                 and (num_xcc <= 0 or len(xccs) == num_xcc))
+    return out
+
+
+def float_tolerance(want: float, digits: int) -> float:
+    """What a value printed with `digits` decimals may differ by after parsing:
+    half a unit of the last digit, plus 1e-9 relative for the few double
+    operations whose order may differ."""
+    return 0.5 * 10.0 ** -digits + 1e-9 * abs(want)
+
+
+def assert_verdict(got: dict, want: dict, float_digits: dict, what: str = "") -> None:
+    """`got`: a parsed JSON line of the probe; `want`: sweep_verdict / perf_verdict.
+    Integers and booleans equal exactly, printed doubles within float_tolerance."""
+    for key, w in want.items():
+        assert key in got, f"{what}: no {key!r} in {sorted(got)}"
+        g = got[key]
+        if key in float_digits:
+            gs, ws = (g, w) if isinstance(w, list) else ([g], [w])
+            assert len(gs) == len(ws), f"{what}: {key} {g} want {w}"
+            for a, b in zip(gs, ws):
+                assert abs(a - b) <= float_tolerance(b, float_digits[key]), f"{what}: {key} {g} want {w}"
+        else:
+            assert type(g) is type(w) and g == w, f"{what}: {key} {g!r} want {w!r}"

@@ -6,7 +6,9 @@ wrote, saved as .npy, with guard regions around every buffer.
 REQUESTS.json is a list of requests, run in order:
 
     {"id": ..., "kernel": "liveness", "nonce": n, "iters": k}
-    {"id": ..., "kernel": "sweep", "nonce": n, "iters": k, "grid": g, "wait_ticks": t}
+    {"id": ..., "kernel": "sweep", "nonce": n, "iters": k, "grid": g, "wait_ticks": t[, "args_grid": a]}
+        (g workgroups are launched and sized for; the kernel is told a, default g: with a > g the
+        residency wait can only end at wait_ticks)
     {"id": ..., "kernel": "hbm_fill", "n16": u, "grid": g, "threads": t, "seed": s, "poison_unit": p | null}
     {"id": ..., "kernel": "hbm_check", "n16": u, "grid": g, "threads": t, "seed": s, "buf_npy": file}
     {"id": ..., "kernel": "burn", "nonce": n, "iters": k, "grid": g, "hbm_counters": [4 words]}
@@ -143,8 +145,9 @@ def plan(req: dict, base_dir: Path):
         g = int(req["grid"])
         bufs = [("records", np.uint32, _filled(g * 16 * 4, 0)), ("tiles", np.float32, _filled(g * 32 * 32 * 4, OUT_PREFILL)),
                 ("arrive", np.uint32, _filled(4, 0))]
-        return bufs, lambda p: SweepArgs(p["records"], p["tiles"], p["arrive"], req["nonce"], req["iters"], g,
-                                         req["wait_ticks"]), g
+        args_grid = int(req.get("args_grid", g))
+        return bufs, lambda p: SweepArgs(p["records"], p["tiles"], p["arrive"], req["nonce"], req["iters"],
+                                         args_grid, req["wait_ticks"]), g
     if k in ("hbm_fill", "hbm_check"):
         n16 = int(req["n16"])
         if k == "hbm_fill":

@@ -57,16 +57,19 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None):
 def _perf_device(ordinal_reported, mode, nonce, host_ordinal=None):
     """Throughput-check reply (kind "perf"); modes from the control file's
     "perf" map: slow_hbm, slow_mfma, slow_xcd (one XCD at a third of the clock),
+    slow_xcd_after_absent (five entries, XCD 0 reports no clock, XCD 3 is slow),
     corrupt (HBM words read back wrong); hang (the server never answers; serve mode only)."""
     xcd = [1530.0] * 8
     if mode == "slow_xcd":
         xcd[3] = 510.0
+    if mode == "slow_xcd_after_absent":
+        xcd = [0.0, 2400.0, 2400.0, 900.0, 2400.0]
     d = {**_identity(ordinal_reported if host_ordinal is None else host_ordinal),
          "ordinal": ordinal_reported, "ok": mode != "corrupt", "hsa_error": 0, "nonce": nonce, "bytes": 4 << 30,
          "cu_count": 256, "num_xcc": 8, "hbm_write_gbps": 4600.0, "hbm_read_gbps": 1500.0 if mode == "slow_hbm" else 6000.0,
          "hbm_bad_words": 3 if mode == "corrupt" else 0, "hbm_first_bad": 4096 if mode == "corrupt" else -1,
          "mfma_iters": 65536, "mfma_grid": 512, "mfma_records_ok": 512, "mfma_checksum_mismatch": 0, "mfma_xccs": 8,
-         "mfma_tflops": 400.0 if mode == "slow_mfma" else 1550.0, "clock_mhz_min": min(xcd), "clock_mhz_median": 1530.0,
+         "mfma_tflops": 400.0 if mode == "slow_mfma" else 1550.0, "clock_mhz_min": min(c for c in xcd if c > 0), "clock_mhz_median": 1530.0,
          "clock_mhz_max": max(xcd), "xcd_clock_mhz": xcd, "total_us": 35000.0, "in_flight_s": 0.0,
          "error": "hbm_bad_words=3 first_bad_unit=4096" if mode == "corrupt" else ""}
     return d

@@ -6,7 +6,12 @@ no torch) runs one request list; every test asserts on the arrays it saved.
 If the child stopped early, the tests whose arrays are missing fail with its
 stderr, and nothing else is launched. The comparisons live in
 kernel_reference.py; tests/test_kernel_reference.py shows on the CPU that each
-of them fails on the output of a wrong kernel."""
+of them fails on the output of a wrong kernel.
+
+The same arrays then go through the shipped verdicts (chip_verify.h, by way of
+the kernel_contract_cli program the native build produced): what a real kernel
+wrote must come out `ok`, equal to the reference verdict field by field, and
+stop being `ok` with one bit flipped on the host."""
 import json
 import os
 import subprocess
@@ -16,6 +21,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from rocm_k8s_device_plugin_amd.testing import contract_cli
 from rocm_k8s_device_plugin_amd.testing import kernel_reference as ref
 from rocm_k8s_device_plugin_amd.testing import raw_kernels
 
@@ -51,6 +57,8 @@ CHECK_CASES = {
 BURN_GRID = 2
 BURN_CASES = [(n, it) for n in ref.BURN_NONCES for it in ref.BURN_ITERS]
 BURN_COUNTERS = [0xC0FFEE01, 0, 0xFFFFFFFF, 0x12345678]
+# the kernel is told of one workgroup more than is launched: the residency wait ends at its time limit
+SHORT_GRID_ID, SHORT_GRID_NONCE, SHORT_GRID_ITERS, SHORT_GRID_WAIT_TICKS = "sweep_short_grid", 0xFFFFFFFF, 4, 20000
 
 
 def _live_id(n, it):
@@ -85,6 +93,8 @@ def _requests(work: Path):
     # last: the 160 KiB-LDS kernel has otherwise only been dispatched through ROCr
     reqs += [{"id": _sweep_id(n, it), "kernel": "sweep", "nonce": n, "iters": it, "grid": SWEEP_GRID,
               "wait_ticks": SWEEP_WAIT_TICKS} for n, it in SWEEP_CASES]
+    reqs.append({"id": SHORT_GRID_ID, "kernel": "sweep", "nonce": SHORT_GRID_NONCE, "iters": SHORT_GRID_ITERS,
+                 "grid": SWEEP_GRID, "args_grid": SWEEP_GRID + 1, "wait_ticks": SHORT_GRID_WAIT_TICKS})
     return reqs
 
 
@@ -176,20 +186,103 @@ def test_hbm_check_counts_words_and_finds_the_first_unit(run, name):
     ref.assert_bit_equal(run.load(rid, "buf"), np.load(run.outdir.parent / f"{rid}.input.npy"), "buf")
 
 
+def _record_in_box(run, **figures):
+    """Measured figures go to raw_kernels_box.json, in $MI355X_BOX_DIR when it is set (the
+    directory a GPU run's records are collected from), else next to the arrays."""
+    box_dir = Path(os.environ.get("MI355X_BOX_DIR") or run.outdir.parent)
+    box_dir.mkdir(parents=True, exist_ok=True)
+    path = box_dir / "raw_kernels_box.json"
+    box = json.loads(path.read_text()) if path.exists() else {}
+    box.update(figures)
+    path.write_text(json.dumps(box, indent=1))
+
+
 def test_mfma_burn_records_and_checksum(run):
     got = {(n, it): run.load(_burn_id(n, it), "records") for n, it in BURN_CASES}
     box = [{"nonce": n, "iters": it, "gpu": ref.burn_gpu_checksum(rec), "reference": ref.burn_checksum(n, it)[0],
             "bound": ref.burn_bound(it, ref.burn_checksum(n, it)[1]),
             "abs_diff_over_bound": ref.burn_ratio(rec, n, it)} for (n, it), rec in got.items()]
-    # the measured figures are recorded before anything is asserted: in $MI355X_BOX_DIR
-    # when it is set (the directory a GPU run's records are collected from), else next to the arrays
-    box_dir = Path(os.environ.get("MI355X_BOX_DIR") or run.outdir.parent)
-    box_dir.mkdir(parents=True, exist_ok=True)
-    with open(box_dir / "raw_kernels_box.json", "w") as f:
-        json.dump({"burn_margin": ref.BURN_MARGIN, "burn": box}, f, indent=1)
+    _record_in_box(run, burn_margin=ref.BURN_MARGIN, burn=box)     # before anything is asserted
     print("burn |gpu - ref| / bound:", [round(b["abs_diff_over_bound"], 4) for b in box])
     for (n, it), rec in got.items():
         rid = _burn_id(n, it)
         ref.check_burn(rec, run.load(rid, "hbm_counters_host"), np.array(BURN_COUNTERS, dtype=np.uint32), n, it,
                        BURN_GRID)
         ref.assert_bit_equal(run.load(rid, "hbm_counters"), np.array(BURN_COUNTERS, dtype=np.uint32), "hbm_counters")
+
+
+# ---- the same bytes through the shipped verdicts ------------------------------------------------
+@pytest.fixture(scope="module")
+def cli(tmp_path_factory):
+    return contract_cli.contract_cli(tmp_path_factory.mktemp("kernel_contract"))
+
+
+@pytest.mark.parametrize("nonce,iters", SWEEP_CASES)
+def test_sweep_verdict_on_what_the_kernel_wrote(run, cli, nonce, iters):
+    rid = _sweep_id(nonce, iters)
+    records, tiles = run.load(rid, "records"), run.load(rid, "tiles")
+    bits = tiles.view(np.uint32)
+    flipped = [(contract_cli.TILES, 2 * 1024 + 517, int(bits[2 * 1024 + 517]) ^ 1 << 22)]
+    case = dict(grid=SWEEP_GRID, nonce=nonce, iters=iters)
+    unknown, flip, eight = contract_cli.sweep_verdicts(
+        cli, [contract_cli.sweep_case(records, tiles, num_xcc=0, variants=[flipped], **case),
+              contract_cli.sweep_case(records, tiles, num_xcc=8, **case)], 3)
+    print("sweep verdict:", unknown)
+    ref.assert_verdict(unknown, ref.sweep_verdict(records, tiles, num_xcc=0, **case), ref.SWEEP_FLOAT_DIGITS, rid)
+    # four workgroups that each hold a CU's whole LDS cannot share a CU
+    assert unknown["ok"] is True and unknown["records_ok"] == 4 and unknown["cus_covered"] == 4, unknown
+    assert unknown["error"] == ""
+    xcc_words = {int(x) for x in records.reshape(SWEEP_GRID, 16)[:, ref.REC_XCC]}
+    assert unknown["xccs_covered"] == len(xcc_words), (unknown, xcc_words)
+    # four workgroups cannot cover eight XCDs
+    ref.assert_verdict(eight, ref.sweep_verdict(records, tiles, num_xcc=8, **case), ref.SWEEP_FLOAT_DIGITS, rid)
+    assert eight["ok"] is False and eight["records_ok"] == 4 and "/8 XCDs ran" in eight["error"], eight
+    wrong = tiles.copy()
+    wrong.view(np.uint32)[2 * 1024 + 517] ^= np.uint32(1 << 22)
+    ref.assert_verdict(flip, ref.sweep_verdict(records, wrong, num_xcc=0, **case), ref.SWEEP_FLOAT_DIGITS, rid)
+    assert flip["ok"] is False and flip["tile_bad"] == 1 and flip["records_ok"] == 3, flip
+
+
+PERF_TIMES = dict(fill_us=11.3, check_us=9.7, check2_us=8.3, mfma_us=21.3)
+
+
+@pytest.mark.parametrize("nonce,iters", BURN_CASES)
+def test_perf_verdict_on_what_the_kernel_wrote(run, cli, nonce, iters):
+    rid = _burn_id(nonce, iters)
+    records = run.load(rid, "records")
+    params = dict(burn_wgs=BURN_GRID, nonce=nonce, num_xcc=0, bytes=16 * HBM_N16, mfma_iters=iters, **PERF_TIMES)
+    # what the check kernel counted for three corrupted units and for the last unit's last word
+    found = []
+    for name, bad, first in (("three_units", 3, 700), ("last_unit_word3", 1, HBM_N16 - 1)):
+        counted = int(run.load(f"check_{name}", "bad")[0])
+        unit = int(run.load(f"check_{name}", "first_bad")[0])
+        found.append((name, bad, first, [counted, 0, unit & 0xFFFFFFFF, unit >> 32]))
+    variants = [[(contract_cli.COUNTERS, i, w) for i, w in enumerate(words)] for _, _, _, words in found]
+    clean = [0, 0, 0xFFFFFFFF, 0xFFFFFFFF]
+    got = contract_cli.perf_verdicts(cli, [contract_cli.perf_case(records, clean, variants=variants, **params)], 3)
+    print("perf verdict:", got[0])
+    ref.assert_verdict(got[0], ref.perf_verdict(records, clean, **params), ref.PERF_FLOAT_DIGITS, rid)
+    assert got[0]["ok"] is True and got[0]["mfma_records_ok"] == 2 and got[0]["mfma_checksum_mismatch"] == 0, got[0]
+    assert got[0]["hbm_first_bad"] == -1 and got[0]["error"] == ""
+    assert got[0]["clock_mhz_min"] > 0 and got[0]["clock_mhz_median"] > 0 and got[0]["clock_mhz_max"] > 0, got[0]
+    for (name, bad, first, words), d in zip(found, got[1:]):
+        ref.assert_verdict(d, ref.perf_verdict(records, words, **params), ref.PERF_FLOAT_DIGITS, f"{rid} {name}")
+        assert d["ok"] is False and d["hbm_bad_words"] == bad and d["hbm_first_bad"] == first, (name, d)
+        assert d["mfma_records_ok"] == 2 and f"hbm_bad_words={bad} first_bad_unit={first} " in d["error"], (name, d)
+
+
+def test_sweep_residency_wait_ends_at_its_time_limit(run):
+    """The kernel is told of SWEEP_GRID + 1 workgroups and SWEEP_GRID are launched: nobody ever
+    sees the whole grid, so every workgroup leaves the wait through `elapsed > wait_ticks`, the
+    exit a production sweep takes when another tenant holds a CU."""
+    records, tiles = run.load(SHORT_GRID_ID, "records"), run.load(SHORT_GRID_ID, "tiles")
+    recs = [[int(x) for x in row] for row in records.reshape(SWEEP_GRID, 16)]
+    waited = [(r[ref.REC_T1_LO] | r[ref.REC_T1_HI] << 32) - (r[ref.REC_T0_LO] | r[ref.REC_T0_HI] << 32) for r in recs]
+    arrived = [r[ref.REC_ARRIVED] for r in recs]
+    _record_in_box(run, sweep_short_grid={"wait_ticks": SHORT_GRID_WAIT_TICKS, "t1_minus_t0_ticks": waited,
+                                          "largest_t1_minus_t0_ticks": max(waited), "arrived": arrived})
+    print("short grid: t1 - t0 ticks", waited, "arrived", arrived)
+    ref.check_sweep(records, tiles, SHORT_GRID_NONCE, SHORT_GRID_ITERS, SWEEP_GRID)
+    assert all(1 <= a <= SWEEP_GRID for a in arrived), arrived
+    assert int(run.load(SHORT_GRID_ID, "arrive")[0]) == SWEEP_GRID
+    assert all(w > SHORT_GRID_WAIT_TICKS for w in waited), waited      # straight from the loop condition

@@ -5,9 +5,8 @@ and the comparisons the GPU tests apply (tests/test_gpu_kernels_raw.py) fail
 on the output of a wrong kernel.
 
 The header and verify_tile are reached through native/tests/kernel_contract_cli.cpp,
-a host-only program compiled here by the C++ compiler."""
-import os
-import shutil
+a host-only program: the one the native build produced, or compiled here by
+the C++ compiler (testing/contract_cli.py)."""
 import struct
 import subprocess
 from pathlib import Path
@@ -15,6 +14,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from rocm_k8s_device_plugin_amd.testing import contract_cli
 from rocm_k8s_device_plugin_amd.testing import kernel_reference as ref
 from rocm_k8s_device_plugin_amd.testing import raw_kernels
 
@@ -25,14 +25,7 @@ TILE_CASES = [(n, it) for n in NONCES for it in ITERS]
 
 @pytest.fixture(scope="module")
 def cli(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path_factory.mktemp("kernel_contract") / "kernel_contract_cli"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-I", str(REPO / "native" / "include"),
-                    "-I", str(REPO / "native" / "src" / "health"),
-                    str(REPO / "native" / "tests" / "kernel_contract_cli.cpp"), "-o", str(exe)],
-                   check=True, timeout=120)
-    return exe
+    return contract_cli.contract_cli(tmp_path_factory.mktemp("kernel_contract"))
 
 
 def _gen(cli, lines):

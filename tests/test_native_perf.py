@@ -94,6 +94,21 @@ def test_perf_floors_scale_with_partition(tmp_path):
         eng.close()
 
 
+def test_perf_names_the_slow_xcd_by_its_id(tmp_path):
+    """XCD 0 reports no clock: the slow one is still XCD 3, not the third of those that did."""
+    fi, ctl, eng, dev = _engine(tmp_path, {"perf": {"2": "slow_xcd_after_absent"}})
+    try:
+        assert eng.perf_problems({"cu_count": 256, "hbm_read_gbps": 6000.0, "hbm_write_gbps": 4600.0,
+                                  "mfma_tflops": 1550.0, "xcd_clock_mhz": [0, 2400, 2400, 900, 2400]}) == [
+            "XCD 3 at 900 MHz vs median 2400 MHz under MFMA load"]
+        eng.sweep()
+        perf = eng.perf_verdicts()
+        assert perf[dev[2]] == ("degraded", "throughput check: XCD 3 at 900 MHz vs median 2400 MHz under MFMA load")
+        assert perf[dev[0]] == ("ok", "")
+    finally:
+        eng.close()
+
+
 def test_perf_spawn_mode(tmp_path):
     """Without the server the check runs per device in a fresh process (--perf)."""
     fi, ctl, eng, dev = _engine(tmp_path, {"perf": {"2": "corrupt", "1": "slow_mfma"}}, persistent=False)
