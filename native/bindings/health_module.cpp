@@ -54,6 +54,7 @@ class PyHealthEngine {
     i("chip_sweep_every", &c.chip_sweep_every);
     i("perf_check_every", &c.perf_check_every);
     s("perf_action", &c.perf_action);
+    i("datapath_check_every", &c.datapath_check_every);
     d("perf_min_hbm_read_gbps", &c.perf_min_hbm_read_gbps);
     d("perf_min_hbm_write_gbps", &c.perf_min_hbm_write_gbps);
     d("perf_min_mfma_tflops", &c.perf_min_mfma_tflops);
@@ -106,6 +107,8 @@ class PyHealthEngine {
     d["version"] = eng_->version();
     d["chip_sweeps"] = eng_->chip_sweeps();
     d["perf_checks"] = eng_->perf_checks();
+    d["datapath_checks"] = eng_->datapath_checks();
+    d["datapath_failures"] = eng_->datapath_failures();
     if (auto* p = eng_->prober()) {
       d["server_starts"] = p->server_starts.load();
       d["server_restarts"] = p->server_restarts.load();

@@ -193,6 +193,10 @@ struct Config {
   // MI355X, scaled by the device's CU share; "unhealthy" withdraws degraded GPUs
   int perf_check_every = 0;
   std::string perf_action = "report";
+  // every N-th sweep (and the first): the MFMA datapath check (full-width
+  // operands, bit-exact) on idle, live GPUs; a failed verdict makes the device
+  // Unhealthy until a later check passes (0 = off)
+  int datapath_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_hbm_write_gbps = 2000.0;
   double perf_min_mfma_tflops = 700.0;
@@ -251,6 +255,10 @@ class Engine {
   uint64_t crowded_skips() const { return crowded_skips_; }
   uint64_t chip_sweeps() const { return chip_sweeps_; }
   uint64_t perf_checks() const { return perf_checks_; }
+  uint64_t datapath_checks() const { return datapath_checks_; }
+  uint64_t datapath_failures() const { return datapath_failures_; }
+  // device -> why its last MFMA datapath check failed (absent: it passed, or never ran)
+  std::map<std::string, std::string> datapath_failed() const;
   // device -> (ok | degraded | failed, reason) of its last throughput check
   std::map<std::string, std::pair<std::string, std::string>> perf_verdicts() const;
   std::map<std::string, ProbeOutcome> perf_last() const;  // device -> its last throughput-check reply
@@ -298,6 +306,7 @@ class Engine {
   const GpuDevice* dev(const std::string& id) const;
   bool fabric_check();  // false: no xGMI link reading this sweep
   void perf_check(const std::map<std::string, int>& ords);
+  void datapath_check(const std::map<std::string, int>& ords);
   SmiXgmiSnapshot read_xgmi();
 
   std::vector<GpuDevice> devices_;
@@ -318,6 +327,8 @@ class Engine {
   uint64_t sweeps_ = 0, identity_remaps_ = 0, crowded_skips_ = 0, chip_sweeps_ = 0, perf_checks_ = 0;
   std::map<std::string, std::pair<std::string, std::string>> perf_;  // guarded by mu_
   std::map<std::string, ProbeOutcome> perf_last_;                     // guarded by mu_
+  uint64_t datapath_checks_ = 0, datapath_failures_ = 0;
+  std::map<std::string, std::string> datapath_failed_;                // guarded by mu_
   uint64_t xgmi_readings_ = 0;
   double last_sweep_ms_ = 0;
   int abort_fd_ = -1;

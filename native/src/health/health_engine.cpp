@@ -501,7 +501,16 @@ void Engine::liveness_pass(Reasons* reasons) {
       if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = o;
     if (!cand.empty()) perf_check(cand);
   }
+  // the same idle GPUs, under the same rule: `idle` is empty while busy state is unknown
+  if (cfg_.datapath_check_every > 0 && sweeps_ % static_cast<uint64_t>(cfg_.datapath_check_every) == 0) {
+    std::map<std::string, int> cand;
+    for (const auto& [id, o] : probe_ords)
+      if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = o;
+    if (!cand.empty()) datapath_check(cand);
+  }
   std::lock_guard<std::mutex> lk(mu_);
+  for (const auto& [id, why] : datapath_failed_)
+    if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
     if (reasons->count(id) && (pv.first == "failed" || (pv.first == "degraded" && cfg_.perf_action == "unhealthy")))
       (*reasons)[id].push_back(pv.second);
@@ -919,6 +928,49 @@ void Engine::perf_check(const std::map<std::string, int>& ords) {
               "last throughput check: median shader clock per XCD");
     }
   }
+}
+
+// The MFMA datapath check on idle GPUs: a reply that is not ok (the verdict
+// names stage, word and xor of the first wrong word) makes the device
+// Unhealthy until a later check passes.
+void Engine::datapath_check(const std::map<std::string, int>& ords) {
+  trace::Span span("health.datapath_check", "health", {{"devices", std::to_string(ords.size())}});
+  std::vector<int> uniq;
+  for (const auto& [id, o] : ords) uniq.push_back(o);
+  const auto by_ord = prober_->probe(uniq, {}, "datapath");
+  datapath_checks_++;
+  auto& m = metrics::global();
+  m.inc("mi355x_dp_datapath_checks_total", {}, 1.0,
+        "MFMA datapath checks run (full-width operands, bit-exact, on the idle GPUs)");
+  for (const auto& [id, ord] : ords) {
+    auto it = by_ord.find(ord);
+    if (it == by_ord.end()) continue;
+    const ProbeOutcome& o = it->second;
+    if (o.interrupted) continue;  // stopped by the shutdown, not failed: the last result stands
+    const std::string why = o.ok ? std::string() : "datapath check: " + o.reason;
+    bool was_failed;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      was_failed = datapath_failed_.count(id) > 0;
+      if (o.ok)
+        datapath_failed_.erase(id);
+      else
+        datapath_failed_[id] = why;
+    }
+    if (!o.ok) {
+      datapath_failures_++;
+      m.inc("mi355x_dp_datapath_check_failures_total", {{"device", id}}, 1.0,
+            "MFMA datapath checks that did not pass");
+    }
+    if (was_failed != !o.ok)
+      glog::log(o.ok ? glog::kInfo : glog::kWarning, __FILE__, __LINE__, "device %s: datapath check %s %s", id.c_str(),
+                o.ok ? "passes again" : "failed:", why.c_str());
+  }
+}
+
+std::map<std::string, std::string> Engine::datapath_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_failed_;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

@@ -1,8 +1,9 @@
 // The full-chip sweep (mi355x_hsa_chip_sweep: every CU of every XCD runs the
-// MFMA tile and reports where it ran) and the throughput check
+// MFMA tile and reports where it ran), the throughput check
 // (mi355x_hsa_perf_check: HBM write / read over a verified pattern, sustained
-// bf16 MFMA rate, per-XCD clocks), both on the device's kept queue when there
-// is one. A dispatch that outlives its deadline is parked in an in-flight
+// bf16 MFMA rate, per-XCD clocks) and the MFMA datapath check
+// (mi355x_hsa_datapath_check: full-width operands, bit-exact), all on the
+// device's kept queue when there is one. A dispatch that outlives its deadline is parked in an in-flight
 // registry with everything it may still write.
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "chip_verify.h"
+#include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_verify.h"
 
@@ -510,6 +512,126 @@ extern "C" int mi355x_hsa_perf_check(int ordinal, uint32_t nonce, uint64_t bytes
   out->mfma_us = dispatch_us(ag, w.sig->s);
 #undef PERF_CHECK
   mi355x::perf_verdict(records, h_counters, burn_wgs, out);
+  free_bufs();
+  return finish();
+}
+
+namespace mi355x::hsa_rt {
+// --corrupt-datapath: stage < 0 = off
+std::mutex g_dp_corrupt_mu;
+int g_dp_corrupt[4] = {-1, 0, 0, -1};  // stage, word, bit, ordinal
+}  // namespace mi355x::hsa_rt
+
+extern "C" void mi355x_hsa_datapath_corrupt(int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  g_dp_corrupt[0] = stage;
+  g_dp_corrupt[1] = word;
+  g_dp_corrupt[2] = bit;
+  g_dp_corrupt[3] = ordinal;
+}
+
+extern "C" int mi355x_hsa_datapath_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_result* out) {
+  using clk = std::chrono::steady_clock;
+  std::memset(out, 0, sizeof(*out));
+  out->ordinal = ordinal;
+  out->nonce = nonce;
+  out->first_bad_wg = out->first_bad_stage = out->first_bad_word = -1;
+  const auto t0 = clk::now();
+  auto finish = [&] {
+    out->total_us = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
+    return out->ok ? 0 : 1;
+  };
+  const int n = mi355x_hsa_probe_init();
+  if (n < 0) {
+    out->hsa_error = n;
+    std::snprintf(out->error, sizeof(out->error), "hsa_init: %.140s", H().loaded ? "runtime init failed" : H().error);
+    return 1;
+  }
+  if (ordinal < 0 || ordinal >= n) {
+    std::snprintf(out->error, sizeof(out->error), "no such GPU agent (count=%d)", n);
+    return 1;
+  }
+  if (sweep_still_in_flight(ordinal, out)) return finish();
+  const Agent& ag = g_rt.gpus[ordinal];
+  uint32_t cus = 0, xcc = 0;
+  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT), &cus);
+  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_NUM_XCC), &xcc);
+  out->cu_count = static_cast<int>(cus);
+  out->num_xcc = static_cast<int>(xcc);
+  if (cus == 0 || cus > 1024 || !g_rt.has_fine || !g_rt.has_kernarg) {
+    std::snprintf(out->error, sizeof(out->error), "unexpected agent (cus=%u) or missing memory pool", cus);
+    return 1;
+  }
+  const uint32_t grid = cus;
+  out->grid = static_cast<int>(grid);
+
+  DeviceWork dw(ag);
+  const char* what = "";
+  hsa_status_t s = dw.open(ordinal, &what);
+  if (s != HSA_STATUS_SUCCESS) {
+    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, what);
+    return finish();
+  }
+  out->kept_queue = dw.borrowed() ? 1 : 0;
+  KernelSym ksym;
+  if ((s = dw.symbol("mi355x_mfma_datapath.kd", &ksym)) != HSA_STATUS_SUCCESS) {
+    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, "kernel symbol");
+    return finish();
+  }
+  if (ksym.kseg < sizeof(mi355x_datapath_args) || ksym.kseg > kKernargBytes) {
+    std::snprintf(out->error, sizeof(out->error), "datapath kernarg segment %u: code object / host ABI mismatch",
+                  ksym.kseg);
+    return finish();
+  }
+  uint32_t* records = nullptr;
+  uint32_t* tiles = nullptr;
+  mi355x_datapath_args* kargs = nullptr;
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DP_REC_WORDS * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DP_WG_WORDS * sizeof(uint32_t);
+  auto free_bufs = [&] {
+    if (kargs) H().hsa_amd_memory_pool_free(kargs);
+    if (tiles) H().hsa_amd_memory_pool_free(tiles);
+    if (records) H().hsa_amd_memory_pool_free(records);
+  };
+#define DP_CHECK(expr, label)                                                                 \
+  if ((s = (expr)) != HSA_STATUS_SUCCESS) {                                                   \
+    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, label);                 \
+    free_bufs();                                                                              \
+    return finish();                                                                          \
+  }
+  DP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, rec_bytes, 0, reinterpret_cast<void**>(&records)),
+           "alloc records");
+  DP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, tile_bytes, 0, reinterpret_cast<void**>(&tiles)),
+           "alloc tiles");
+  DP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.kernarg, kKernargBytes, 0, reinterpret_cast<void**>(&kargs)),
+           "alloc kernarg");
+  DP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, records), "allow records");
+  DP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, tiles), "allow tiles");
+  DP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, kargs), "allow kernarg");
+#undef DP_CHECK
+  std::memset(records, 0, rec_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  dw.submit(ksym, kargs, grid, MI355X_DP_THREADS);
+  if (!wait_signal(dw.sig->s, timeout_s)) {
+    std::snprintf(out->error, sizeof(out->error), "datapath check did not complete within %.1fs", timeout_s);
+    out->hsa_error = -1;
+    dw.abandon(ordinal, {kargs, tiles, records}, t0);
+    return finish();
+  }
+  out->kernel_us = dispatch_us(ag, dw.sig->s);
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* c = g_dp_corrupt;
+    if (c[0] >= 0 && c[0] < MI355X_DP_STAGES && c[1] >= 0 && c[1] < MI355X_DP_TILE && c[2] >= 0 && c[2] < 32 &&
+        (c[3] < 0 || c[3] == ordinal))
+      tiles[c[0] * MI355X_DP_TILE + c[1]] ^= 1u << c[2];
+  }
+  mi355x::datapath_verdict(records, tiles, grid, out);
   free_bufs();
   return finish();
 }

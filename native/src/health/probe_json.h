@@ -83,4 +83,18 @@ inline std::string perf_json(const mi355x_perf_result& r) {
       r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", json_escape(r.error).c_str());
 }
 
+inline std::string datapath_json(const mi355x_datapath_result& r) {
+  return json_format(
+      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
+      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u],\"tile_bad\":%u,"
+      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
+      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
+      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"error\":\"%s\"}",
+      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
+      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.tile_bad, r.first_bad_wg,
+      r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered,
+      r.simds_covered, r.xccs_covered, r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false",
+      json_escape(r.error).c_str());
+}
+
 }  // namespace mi355x

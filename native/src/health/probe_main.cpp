@@ -5,9 +5,11 @@
 //   mi355x-liveness-probe --serve [--keep]  (long-lived; requests on stdin, see serve())
 //   mi355x-liveness-probe --sweep [--devices ..]   (every CU of every XCD, see mi355x_chip_sweep)
 //   mi355x-liveness-probe --perf [--perf-mib M]     (HBM bandwidth + pattern, sustained MFMA rate, clocks)
+//   mi355x-liveness-probe --datapath [--devices ..] (full-width bit-exact MFMA operands, see mi355x_mfma_datapath)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
+//   --corrupt-datapath S:W:B[@O]: flip bit B of word W of workgroup 0's stage S tile before the datapath verdict
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -68,6 +70,7 @@ uint64_t mono_ns() {
   return static_cast<uint64_t>(ts.tv_sec) * 1000000000ull + ts.tv_nsec;
 }
 
+using mi355x::datapath_json;
 using mi355x::json_escape;
 using mi355x::perf_json;
 using mi355x::sweep_json;
@@ -116,6 +119,12 @@ int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double timeout_
   return mi355x_hsa_perf_check(o, nonce, bytes, iters, timeout_s, r);
 }
 void perf_poison(uint64_t unit) { mi355x_hsa_perf_poison(unit); }
+int datapath_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_result* r) {
+  return mi355x_hsa_datapath_check(o, nonce, timeout_s, r);
+}
+void datapath_corrupt(int stage, int word, int bit, int ordinal) {
+  mi355x_hsa_datapath_corrupt(stage, word, bit, ordinal);
+}
 void init_phases(double out[5]) { mi355x_hsa_init_phases(out); }
 void defer_teardown() { mi355x_hsa_probe_defer_release(1); }
 void teardown() { mi355x_hsa_probe_release(); }
@@ -145,6 +154,15 @@ int chip_sweep(int o, uint32_t nonce, int iters, double, mi355x_sweep_result* r)
   return 1;
 }
 void perf_poison(uint64_t) {}
+void datapath_corrupt(int, int, int, int) {}
+int datapath_check(int o, uint32_t nonce, double, mi355x_datapath_result* r) {
+  std::memset(r, 0, sizeof(*r));
+  r->ordinal = o;
+  r->nonce = nonce;
+  r->first_bad_wg = r->first_bad_stage = r->first_bad_word = -1;
+  std::snprintf(r->error, sizeof(r->error), "--datapath needs the HSA-direct build (mi355x-liveness-probe)");
+  return 1;
+}
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
   std::memset(r, 0, sizeof(*r));
   r->ordinal = o;
@@ -328,6 +346,43 @@ bool run_perf(const std::vector<int>& ords, const std::vector<uint32_t>& nonces,
   return ok;
 }
 
+// --datapath: the MFMA datapath check on each selected GPU (parallel host threads).
+bool run_datapath(const std::vector<int>& ords, const std::vector<uint32_t>& nonces,
+                  const std::vector<double>& timeouts, int n, std::string& json) {
+  std::vector<mi355x_datapath_result> res(ords.size());
+  std::vector<int> rcs(ords.size(), 1);
+  auto one = [&](size_t i) {
+    if (ords[i] < 0 || ords[i] >= n) {
+      std::memset(&res[i], 0, sizeof(res[i]));
+      res[i].ordinal = ords[i];
+      res[i].first_bad_wg = res[i].first_bad_stage = res[i].first_bad_word = -1;
+      std::snprintf(res[i].error, sizeof(res[i].error), "no such GPU (count=%d)", n);
+      return;
+    }
+    rcs[i] = datapath_check(ords[i], nonces[i], timeouts[i], &res[i]);
+  };
+  std::vector<std::thread> ths;
+  for (size_t i = 0; i < ords.size(); ++i) ths.emplace_back(one, i);
+  for (auto& t : ths) t.join();
+  bool ok = !ords.empty();
+  json = "[";
+  for (size_t i = 0; i < res.size(); ++i) {
+    ok = ok && rcs[i] == 0;
+    if (i) json += ",";
+    json += datapath_json(res[i]);
+  }
+  json += "]";
+  return ok;
+}
+
+// "S:W:B" or "S:W:B@O" of --corrupt-datapath
+bool parse_corrupt_datapath(const char* spec, int out[4]) {
+  out[3] = -1;
+  char tail = 0;
+  const int n = std::sscanf(spec, "%d:%d:%d@%d%c", &out[0], &out[1], &out[2], &out[3], &tail);
+  return n == 3 || n == 4;
+}
+
 std::string devices_json(const std::vector<mi355x_probe_result>& results) {
   std::string o = "[";
   for (size_t i = 0; i < results.size(); ++i) {
@@ -342,6 +397,7 @@ std::string devices_json(const std::vector<mi355x_probe_result>& results) {
 //     [@<id> ]probe <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]sweep <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]perf <mfma_iters> <timeout_s> <mib> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // is answered with one JSON line {"id":..,"ok":..,"t_ready_ns":..,"devices":[..]}
 // ("id" only for a tagged request). A device's own deadline replaces the
 // request's timeout for that device: the plugin gives GPUs that run other
@@ -369,7 +425,7 @@ constexpr int kMaxServeWorkers = 64;  // beyond this a tagged request is answere
 struct ServeRequest {
   bool tagged = false;
   unsigned long long id = 0;
-  std::string kind;  // probe | sweep | perf
+  std::string kind;  // probe | sweep | perf | datapath
   int iters = 0;
   double timeout_s = 0;
   unsigned long long perf_mib = 0;
@@ -392,6 +448,9 @@ bool parse_request(const std::string& line, ServeRequest* r) {
   if (std::strncmp(p, "perf ", 5) == 0) {
     r->kind = "perf";
     parsed = std::sscanf(p, "perf %d %lf %llu %n", &r->iters, &r->timeout_s, &r->perf_mib, &consumed) >= 3;
+  } else if (std::strncmp(p, "datapath ", 9) == 0) {
+    r->kind = "datapath";
+    parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;
   } else if (std::strncmp(p, "sweep ", 6) == 0) {
     r->kind = "sweep";
     parsed = std::sscanf(p, "sweep %d %lf %n", &r->iters, &r->timeout_s, &consumed) >= 2;
@@ -447,6 +506,8 @@ void answer(const ServeRequest& r, int n) {
     ok = run_sweeps(r.ords, r.nonces, r.iters, r.timeouts, n, body);
   } else if (r.kind == "perf") {
     ok = run_perf(r.ords, r.nonces, static_cast<uint64_t>(r.perf_mib) << 20, r.iters, r.timeouts, n, body);
+  } else if (r.kind == "datapath") {
+    ok = run_datapath(r.ords, r.nonces, r.timeouts, n, body);
   } else {
     std::vector<mi355x_probe_result> results;
     ok = run_batch(r.ords, r.nonces, r.iters, r.timeouts, false, n, results);
@@ -456,7 +517,8 @@ void answer(const ServeRequest& r, int n) {
   std::snprintf(head, sizeof(head), "{%s\"ok\":%s,\"hip_device_count\":%d,\"sweep\":%s,\"perf\":%s,\"t_ready_ns\":%llu,",
                 id_field(r).c_str(), ok ? "true" : "false", n, r.kind == "sweep" ? "true" : "false",
                 r.kind == "perf" ? "true" : "false", static_cast<unsigned long long>(mono_ns()));
-  emit_line(std::string(head) + "\"devices\":" + body + "}");
+  // only a datapath reply carries the key: the other replies stay as they were
+  emit_line(std::string(head) + (r.kind == "datapath" ? "\"datapath\":true," : "") + "\"devices\":" + body + "}");
   teardown();  // queues/executables go, the runtime (and the kfd process) stays
 }
 
@@ -569,6 +631,7 @@ int main(int argc, char** argv) {
   bool peer_mode = false;
   bool sweep_mode = false;
   bool perf_mode = false;
+  bool datapath_mode = false;
   uint64_t perf_mib = 4096;
   int perf_iters = 1 << 16;
   uint64_t peer_bytes = 64ull << 20;
@@ -610,6 +673,15 @@ int main(int argc, char** argv) {
       sweep_mode = true;
     } else if (a == "--perf") {
       perf_mode = true;
+    } else if (a == "--datapath") {
+      datapath_mode = true;
+    } else if (a == "--corrupt-datapath") {
+      int c[4];
+      if (!parse_corrupt_datapath(next("--corrupt-datapath"), c)) {
+        std::fprintf(stderr, "--corrupt-datapath must be STAGE:WORD:BIT[@ORDINAL]\n");
+        return 2;
+      }
+      datapath_corrupt(c[0], c[1], c[2], c[3]);
     } else if (a == "--perf-mib") {
       perf_mib = std::strtoull(next("--perf-mib"), nullptr, 0);
     } else if (a == "--perf-iters") {
@@ -632,7 +704,7 @@ int main(int argc, char** argv) {
     } else if (a == "-h" || a == "--help") {
       std::printf("usage: %s [--devices all|0,1,..] [--nonce N] [--iters N] [--identify] [--timeout S] "
                   "[--sample-init PERIOD_US] [--exit shutdown|release|fast] [--serve [--keep]] [--peer [--peer-bytes B] [--peer-reps R]] [--sweep] "
-                  "[--perf [--perf-mib M] [--perf-iters N] [--poison-hbm UNIT]] "
+                  "[--perf [--perf-mib M] [--perf-iters N] [--poison-hbm UNIT]] [--datapath [--corrupt-datapath S:W:B[@ORDINAL]]] "
                   "[--corrupt-word K[@ORDINAL]] [--hip-stream own|null]\n",
                   argv[0]);
       return 0;
@@ -687,6 +759,16 @@ int main(int argc, char** argv) {
     std::string body;
     const bool ok = run_perf(ords, nonces, perf_mib << 20, perf_iters, timeouts, n, body);
     std::printf("{\"ok\":%s,\"perf\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
+                "\"t_ready_ns\":%llu,\"devices\":%s}\n",
+                ok ? "true" : "false", n, static_cast<unsigned long long>(t_start),
+                static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(mono_ns()), body.c_str());
+    std::fflush(stdout);
+    return ok ? 0 : 1;
+  }
+  if (datapath_mode) {
+    std::string body;
+    const bool ok = run_datapath(ords, nonces, timeouts, n, body);
+    std::printf("{\"ok\":%s,\"datapath\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
                 "\"t_ready_ns\":%llu,\"devices\":%s}\n",
                 ok ? "true" : "false", n, static_cast<unsigned long long>(t_start),
                 static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(mono_ns()), body.c_str());

@@ -1,0 +1,149 @@
+// Host-only view of the MFMA datapath check's contract (datapath_kernel.h) and
+// of its verdict (datapath_verify.h), for tests/test_native_datapath.py and
+// tests/test_gpu_datapath.py. No HIP, no GPU.
+//
+//   datapath_contract_cli gen     < requests    one unsigned word per request line:
+//        a stage i k nw | b stage k j nw | c stage i j nw | wave_nonce nonce wg wave
+//   datapath_contract_cli layout                "struct field offset" / "struct sizeof n" / "define NAME n" lines
+//   datapath_contract_cli verdict < cases       datapath_json lines of mi355x::datapath_verdict. A case:
+//        uint32 grid, nonce, variants; grid*16 record words; grid*4096 tile words; then per variant:
+//        uint32 n and n patches (uint32 array, index, value), array 0 = records, 1 = tiles. One line
+//        for the case as given, then one per variant: the case with that variant's words replaced
+//        (each variant starts from the case as given).
+#include <cinttypes>
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "datapath_kernel.h"
+#include "datapath_verify.h"
+#include "probe_json.h"
+
+static int cmd_gen() {
+  char line[256];
+  while (std::fgets(line, sizeof(line), stdin)) {
+    char name[32];
+    unsigned long long s = 0, x = 0, y = 0, z = 0;
+    const int n = std::sscanf(line, "%31s %llu %llu %llu %llu", name, &s, &x, &y, &z);
+    if (n < 1) continue;
+    const std::string g = name;
+    const bool idx_ok = s < MI355X_DP_STAGES && x < 32 && y < 32;
+    if (g == "a" && n == 5 && idx_ok && y < MI355X_DP_K) {
+      std::printf("%" PRIu32 "\n", dp_a_word((uint32_t)s, (uint32_t)x, (uint32_t)y, (uint32_t)z));
+    } else if (g == "b" && n == 5 && idx_ok && x < MI355X_DP_K) {
+      std::printf("%" PRIu32 "\n", dp_b_word((uint32_t)s, (uint32_t)x, (uint32_t)y, (uint32_t)z));
+    } else if (g == "c" && n == 5 && idx_ok) {
+      std::printf("%" PRIu32 "\n", dp_c_word((uint32_t)s, (uint32_t)x, (uint32_t)y, (uint32_t)z));
+    } else if (g == "wave_nonce" && n == 4) {
+      std::printf("%" PRIu32 "\n", dp_wave_nonce((uint32_t)s, (uint32_t)x, (uint32_t)y));
+    } else {
+      std::fprintf(stderr, "bad gen request: %s", line);
+      return 2;
+    }
+  }
+  return 0;
+}
+
+#define FIELD(S, F) std::printf("%s %s %zu\n", #S, #F, offsetof(S, F))
+#define SIZE(S) std::printf("%s sizeof %zu\n", #S, sizeof(S))
+#define DEFINE(N) std::printf("define %s %llu\n", #N, static_cast<unsigned long long>(N))
+
+static int cmd_layout() {
+  FIELD(mi355x_datapath_args, records);
+  FIELD(mi355x_datapath_args, tiles);
+  FIELD(mi355x_datapath_args, nonce);
+  FIELD(mi355x_datapath_args, grid);
+  SIZE(mi355x_datapath_args);
+  DEFINE(MI355X_DP_THREADS);
+  DEFINE(MI355X_DP_STAGES);
+  DEFINE(MI355X_DP_WG_WORDS);
+  DEFINE(MI355X_DP_REC_WORDS);
+  DEFINE(MI355X_DP_MAGIC);
+  DEFINE(MI355X_DPREC_MAGIC);
+  DEFINE(MI355X_DPREC_WG);
+  DEFINE(MI355X_DPREC_NONCE);
+  DEFINE(MI355X_DPREC_XCC);
+  DEFINE(MI355X_DPREC_HWID);
+  DEFINE(MI355X_DPREC_BAD);
+  return 0;
+}
+
+static constexpr uint32_t kMaxWgs = 4096;  // mi355x_hsa_datapath_check refuses more than 1024 CUs
+
+template <typename T>
+static bool read_n(T* dst, size_t n) {
+  return std::fread(dst, sizeof(T), n, stdin) == n;
+}
+
+struct Patch {
+  uint32_t array, index, value;
+};
+
+static int cmd_verdict() {
+  struct {
+    uint32_t grid, nonce, variants;
+  } h;
+  size_t got;
+  while ((got = std::fread(&h, 1, sizeof(h), stdin)) == sizeof(h)) {
+    if (h.grid == 0 || h.grid > kMaxWgs) {
+      std::fprintf(stderr, "datapath case: grid %u\n", h.grid);
+      return 2;
+    }
+    std::vector<uint32_t> records(static_cast<size_t>(h.grid) * MI355X_DP_REC_WORDS);
+    std::vector<uint32_t> tiles(static_cast<size_t>(h.grid) * MI355X_DP_WG_WORDS);
+    if (!read_n(records.data(), records.size()) || !read_n(tiles.data(), tiles.size())) {
+      std::fprintf(stderr, "truncated datapath case\n");
+      return 2;
+    }
+    auto run = [&] {
+      mi355x_datapath_result r;
+      std::memset(&r, 0, sizeof(r));
+      r.nonce = h.nonce;
+      r.grid = static_cast<int>(h.grid);
+      mi355x::datapath_verdict(records.data(), tiles.data(), h.grid, &r);
+      std::printf("%s\n", mi355x::datapath_json(r).c_str());
+    };
+    run();
+    std::vector<uint32_t>* const arrays[2] = {&records, &tiles};
+    for (uint32_t v = 0; v < h.variants; ++v) {
+      uint32_t n = 0;
+      if (!read_n(&n, 1) || n > (1u << 24)) {
+        std::fprintf(stderr, "bad datapath variant %u\n", v);
+        return 2;
+      }
+      std::vector<Patch> patches(n);
+      if (n && !read_n(patches.data(), n)) {
+        std::fprintf(stderr, "truncated datapath variant %u\n", v);
+        return 2;
+      }
+      for (const Patch& p : patches)
+        if (p.array > 1 || p.index >= arrays[p.array]->size()) {
+          std::fprintf(stderr, "datapath variant %u: patch out of range\n", v);
+          return 2;
+        }
+      std::vector<uint32_t> saved(n);
+      for (uint32_t i = 0; i < n; ++i) {
+        saved[i] = (*arrays[patches[i].array])[patches[i].index];
+        (*arrays[patches[i].array])[patches[i].index] = patches[i].value;
+      }
+      run();
+      for (uint32_t i = n; i-- > 0;) (*arrays[patches[i].array])[patches[i].index] = saved[i];
+    }
+  }
+  if (got != 0) {
+    std::fprintf(stderr, "truncated datapath header: %zu bytes\n", got);
+    return 2;
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  const std::string cmd = argc > 1 ? argv[1] : "";
+  if (cmd == "gen") return cmd_gen();
+  if (cmd == "layout") return cmd_layout();
+  if (cmd == "verdict") return cmd_verdict();
+  std::fprintf(stderr, "usage: %s gen|layout|verdict\n", argv[0]);
+  return 2;
+}

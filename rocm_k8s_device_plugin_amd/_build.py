@@ -9,6 +9,7 @@ Outputs land inside the package so they travel with the repo snapshot:
 * ``kernels/liveness_gfx950.hsaco``
 * ``bin/kernel_contract_cli``     host-only driver of the kernel contract and the sweep /
   throughput verdicts (testing/contract_cli.py)
+* ``bin/datapath_contract_cli``   the same for the MFMA datapath check (testing/datapath_reference.py)
 
 ``ensure_built()`` is cheap when everything is up to date (one ninja no-op).
 """
@@ -35,6 +36,7 @@ MOUNTEMU_EXE = PKG_DIR / "bin" / "mi355x-probe-mountemu"
 HIP_DEVEMU_EXE = PKG_DIR / "bin" / "mi355x-probe-hip-devemu"
 HSACO = PKG_DIR / "kernels" / "liveness_gfx950.hsaco"
 CONTRACT_CLI = PKG_DIR / "bin" / "kernel_contract_cli"
+DATAPATH_CLI = PKG_DIR / "bin" / "datapath_contract_cli"
 
 
 def hipcc_available() -> bool:
@@ -207,7 +209,7 @@ def ensure_built(hip: bool | None = None) -> None:
         hip = hipcc_available()
     if hip in _checked:
         return
-    targets = [NATIVE_SO, CONTRACT_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO] if hip else [])
+    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO] if hip else [])
     if not _up_to_date(targets, hip):
         BUILD_DIR.mkdir(parents=True, exist_ok=True)
         with open(BUILD_DIR.parent / ".build.lock", "w") as lk:

@@ -12,6 +12,7 @@ REQUESTS.json is a list of requests, run in order:
     {"id": ..., "kernel": "hbm_fill", "n16": u, "grid": g, "threads": t, "seed": s, "poison_unit": p | null}
     {"id": ..., "kernel": "hbm_check", "n16": u, "grid": g, "threads": t, "seed": s, "buf_npy": file}
     {"id": ..., "kernel": "burn", "nonce": n, "iters": k, "grid": g, "hbm_counters": [4 words]}
+    {"id": ..., "kernel": "datapath", "nonce": n, "grid": g}
 
 For each request OUTDIR gets <id>.<buffer>.npy and <id>.<buffer>.canary.npy
 (2 x CANARY_BYTES: the guard before and after the buffer), and OUTDIR/status.json
@@ -64,10 +65,17 @@ class BurnArgs(ctypes.Structure):
 ARG_STRUCTS = {"mi355x_liveness_args": LivenessArgs, "mi355x_sweep_args": SweepArgs,
                "mi355x_hbm_args": HbmArgs, "mi355x_burn_args": BurnArgs}
 
+class DatapathArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("nonce", _u32), ("grid", _u32)]
+
+
+# the mirrors of datapath_kernel.h (native/tests/datapath_contract_cli.cpp prints that header's layout)
+DATAPATH_ARG_STRUCTS = {"mi355x_datapath_args": DatapathArgs}
+
 # kernel -> (symbol, lanes per workgroup)
 KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_sweep", 256),
            "hbm_fill": ("mi355x_hbm_fill", 256), "hbm_check": ("mi355x_hbm_check", 256),
-           "burn": ("mi355x_mfma_burn", 256)}
+           "burn": ("mi355x_mfma_burn", 256), "datapath": ("mi355x_mfma_datapath", 256)}
 
 _H2D, _D2H = 1, 2
 _LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
@@ -172,6 +180,11 @@ def plan(req: dict, base_dir: Path):
                 ("hbm_counters_host", np.uint32, _filled(16, 0))]
         return bufs, lambda p: BurnArgs(p["records"], p["hbm_counters"], p["hbm_counters_host"], req["nonce"],
                                         req["iters"]), g
+    if k == "datapath":
+        g = int(req["grid"])
+        bufs = [("records", np.uint32, _filled(g * 16 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * 4 * 32 * 32 * 4, OUT_PREFILL))]
+        return bufs, lambda p: DatapathArgs(p["records"], p["tiles"], req["nonce"], g), g
     raise ValueError(f"unknown kernel {k!r}")
 
 

@@ -20,6 +20,9 @@ deadline kill, fallback to per-device isolation, output parsing, nonce check,
 hysteresis. Each start appends a line to $MI355X_STUB_PROBE_LOG if set.
 Throughput-check replies ("perf" requests / --perf) follow the control file's
 "perf" map, e.g. ``{"perf": {"3": "slow_xcd", "4": "corrupt"}}``.
+MFMA datapath-check replies ("datapath" requests / --datapath) follow the
+"datapath" map, e.g. ``{"datapath": {"2": "stuck_bit", "5": "missing"}}``; each
+one appends "datapath:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
 """
 import json
 import os
@@ -75,6 +78,36 @@ def _perf_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return d
 
 
+def _datapath_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """MFMA datapath-check reply (kind "datapath"); modes from the control
+    file's "datapath" map: stuck_bit (bit 30 of every stage-2 word of one CU's
+    tiles stuck: the first wrong word is named), missing (two workgroups wrote
+    no record), device_bad (the device-side compare found mismatches); hang (the
+    server never answers; serve mode only)."""
+    log = os.environ.get("MI355X_STUB_PROBE_LOG")
+    if log:
+        with open(log, "a") as f:
+            f.write(f"datapath:{ordinal_reported if host_ordinal is None else host_ordinal}\n")
+    d = {**_identity(ordinal_reported if host_ordinal is None else host_ordinal),
+         "ordinal": ordinal_reported, "ok": mode == "ok", "hsa_error": 0, "nonce": nonce, "grid": 256, "cu_count": 256,
+         "num_xcc": 8, "records_ok": 256, "mfma_bad": 0, "stage_bad": [0, 0, 0, 0], "tile_bad": 0,
+         "first_bad_wg": -1, "first_bad_stage": -1, "first_bad_word": -1, "first_bad_got": 0, "first_bad_want": 0,
+         "first_bad_xor": 0, "cus_covered": 256, "simds_covered": 1024, "xccs_covered": 8, "kernel_us": 20.0,
+         "total_us": 900.0, "in_flight_s": 0.0, "kept_queue": True, "error": ""}
+    if mode == "stuck_bit":
+        d.update(records_ok=255, tile_bad=498, first_bad_wg=17, first_bad_stage=2, first_bad_word=5,
+                 first_bad_got=0x0A123456, first_bad_want=0x4A123456, first_bad_xor=0x40000000,
+                 error="255/256 workgroups exact (device_bad=0 tile_bad=498); first bad: wg 17 stage 2 word 5 "
+                       "xor 0x40000000 (bit 30)")
+    elif mode == "missing":
+        d.update(records_ok=254, cus_covered=254, simds_covered=1016,
+                 error="254/256 workgroups exact (device_bad=0 tile_bad=0)")
+    elif mode == "device_bad":
+        d.update(records_ok=255, mfma_bad=12, stage_bad=[0, 12, 0, 0],
+                 error="255/256 workgroups exact (device_bad=12 tile_bad=0)")
+    return d
+
+
 def _kfd_entry():
     """Like a kept-queue server: a kfd proc entry with one queue per GPU id
     (MI355X_STUB_KFD_PROC / MI355X_STUB_KFD_GPUIDS), removed on exit.
@@ -108,9 +141,11 @@ def _parse(line):
     if parts and parts[0].startswith("@"):
         rid, parts = int(parts[0][1:]), parts[1:]
     kind = parts[0]
-    timeout = float(parts[2])
+    # "datapath <timeout_s> <device>..." has no iteration count
+    first = {"perf": 4, "datapath": 2}.get(kind, 3)
+    timeout = float(parts[1] if kind == "datapath" else parts[2])
     devs = []
-    for tok in parts[4:] if kind == "perf" else parts[3:]:
+    for tok in parts[first:]:
         f = tok.split(":")
         devs.append((f[0], int(f[1], 0), float(f[2]) if len(f) > 2 and float(f[2]) > 0 else timeout))
     return rid, kind, timeout, devs
@@ -147,6 +182,11 @@ def serve():
             if pmode == "hang":   # a check that never finishes (the daemon stops meanwhile)
                 time.sleep(3600)
             return _perf_device(int(o), pmode, n, host_ordinal=int(hosto))
+        if kind == "datapath":
+            dmode = ctl.get("datapath", {}).get(hosto, "ok")
+            if dmode == "hang":
+                time.sleep(3600)
+            return _datapath_device(int(o), dmode, n, host_ordinal=int(hosto))
         mode = ctl.get(hosto, "ok")
         if mode == "server_fail":
             mode = "fail"
@@ -225,6 +265,8 @@ def serve():
             th.join()
         doc = {"ok": all(d["ok"] for d in res), "hip_device_count": 8, "sweep": kind == "sweep",
                "t_ready_ns": time.monotonic_ns(), "devices": res}
+        if kind == "datapath":
+            doc["datapath"] = True
         if rid is not None:
             doc = {"id": rid, **doc}
         with out_mu:
@@ -259,6 +301,10 @@ def main(argv):
     if "--perf" in argv:
         d = _perf_device(0, _control().get("perf", {}).get(ordinal, "ok"), nonce, host_ordinal=int(ordinal))
         print(json.dumps({"ok": d["ok"], "perf": True, "hip_device_count": 1, "devices": [d]}))
+        return 0 if d["ok"] else 1
+    if "--datapath" in argv:
+        d = _datapath_device(0, _control().get("datapath", {}).get(ordinal, "ok"), nonce, host_ordinal=int(ordinal))
+        print(json.dumps({"ok": d["ok"], "datapath": True, "hip_device_count": 1, "devices": [d]}))
         return 0 if d["ok"] else 1
     ctl = _control()
     mode = ctl.get(ordinal, "ok")
