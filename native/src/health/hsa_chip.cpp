@@ -3,45 +3,50 @@
 // (mi355x_hsa_perf_check: HBM write / read over a verified pattern, sustained
 // bf16 MFMA rate, per-XCD clocks) and the MFMA datapath check
 // (mi355x_hsa_datapath_check: full-width operands, bit-exact), all on the
-// device's kept queue when there is one. A dispatch that outlives its deadline is parked in an in-flight
-// registry with everything it may still write.
+// device's kept queue when there is one. The three share one path: Check
+// (the steps before a check's own part, the timed dispatch, the return
+// conventions), DeviceWork (the queue and executable) and Buffers (the pool
+// memory, owned). A dispatch that outlives its deadline is parked in an
+// in-flight registry with everything it may still write.
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
-#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "chip_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
+#include "probe_json.h"
 #include "probe_verify.h"
 
 using namespace mi355x::hsa_rt;  // NOLINT(build/namespaces)
 
 namespace mi355x::hsa_rt {
+namespace {
 
-// A chip sweep whose completion signal did not fire within its deadline: the
-// dispatch may still write its records, so none of its resources can be freed
-// until it completes. One per device at most (mi355x_hsa_chip_sweep refuses to
-// submit another while it is outstanding).
+// A chip sweep or check whose completion signal did not fire within its
+// deadline: the dispatch may still write its records, so none of its resources
+// can be freed until it completes. One per device at most (Check::begin
+// refuses to submit another while it is outstanding).
 struct SweepInFlight {
   hsa_code_object_reader_t reader{};  // null when the kept queue / executable were borrowed
   hsa_executable_t exe{};
   hsa_queue_t* queue = nullptr;
   std::shared_ptr<SigRef> sig;
-  void* bufs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  std::vector<void*> bufs;  // in allocation order (Buffers::release)
   std::chrono::steady_clock::time_point since{};
 
   void release() {
-    for (void* b : bufs)
-      if (b) H().hsa_amd_memory_pool_free(b);
+    for (auto it = bufs.rbegin(); it != bufs.rend(); ++it) H().hsa_amd_memory_pool_free(*it);
     if (queue) H().hsa_queue_destroy(queue);
     if (exe.handle) H().hsa_executable_destroy(exe);
     if (reader.handle) H().hsa_code_object_reader_destroy(reader);
@@ -50,6 +55,8 @@ struct SweepInFlight {
 };
 std::mutex g_sweep_mu;
 std::vector<std::pair<int, SweepInFlight>> g_sweep_in_flight;
+
+}  // namespace
 
 // > 0 (seconds outstanding) when an earlier sweep or throughput check on
 // `ordinal` is still running; a completed one is freed here.
@@ -68,17 +75,6 @@ double in_flight_for(int ordinal) {
   return 0;
 }
 
-template <typename R>
-bool sweep_still_in_flight(int ordinal, R* out) {
-  const double s = in_flight_for(ordinal);
-  if (s <= 0) return false;
-  out->in_flight_s = s;
-  out->hsa_error = -1;
-  std::snprintf(out->error, sizeof(out->error), "earlier chip sweep / check still in flight for %.1fs (not completed)",
-                s);
-  return true;
-}
-
 // runtime shutdown: an outstanding sweep's resources go with the runtime
 void forget_in_flight_sweeps() {
   std::lock_guard<std::mutex> lk(g_sweep_mu);
@@ -90,9 +86,7 @@ void forget_in_flight_sweeps() {
   g_sweep_in_flight.clear();
 }
 
-}  // namespace mi355x::hsa_rt
-
-namespace mi355x::hsa_rt {
+namespace {
 
 // One AQL kernel dispatch (barrier bit, system-scope fences), no wait.
 void submit_kernel(hsa_queue_t* queue, uint64_t kobj, uint32_t gseg, uint32_t pseg, void* kargs, uint32_t wgs,
@@ -127,9 +121,58 @@ double dispatch_us(const Agent& ag, hsa_signal_t sig) {
   return static_cast<double>(dt.end - dt.start) * 1e6 / static_cast<double>(g_rt.ts_freq);
 }
 
-struct KernelSym {
-  uint64_t kobj = 0;
-  uint32_t kseg = 0, gseg = 0, pseg = 0;
+void set_hsa_error(int* err, char* buf, size_t n, hsa_status_t st, const char* what) {
+  *err = static_cast<int>(st);
+  const char* msg = nullptr;
+  H().hsa_status_string(st, &msg);
+  std::snprintf(buf, n, "%s: %s", what, msg ? msg : "hsa error");
+}
+
+// The pool memory of one check. It frees what it holds, last allocated first,
+// when it goes out of scope -- unless a dispatch that outlived its deadline
+// took it along (release). The first failing step is kept (status, what) and
+// every later step does nothing, so a check sets all its buffers up and then
+// looks at ok() once.
+class Buffers {
+ public:
+  Buffers() = default;
+  Buffers(const Buffers&) = delete;
+  Buffers& operator=(const Buffers&) = delete;
+  ~Buffers() { free(); }
+
+  bool ok() const { return status == HSA_STATUS_SUCCESS; }
+
+  // `bytes` from `pool`; with `allow`, that agent gets access to them
+  template <typename T>
+  T* alloc(hsa_amd_memory_pool_t pool, size_t bytes, const char* label, const Agent* allow = nullptr,
+           const char* allow_label = nullptr) {
+    void* p = nullptr;
+    if (!ok() || !step(H().hsa_amd_memory_pool_allocate(pool, bytes, 0, &p), label)) return nullptr;
+    held_.push_back(p);
+    if (allow) step(H().hsa_amd_agents_allow_access(1, &allow->agent, nullptr, p), allow_label);
+    return static_cast<T*>(p);
+  }
+  void fill(uint32_t* p, uint32_t value, size_t words, const char* label) {
+    if (ok()) step(H().hsa_amd_memory_fill(p, value, words), label);
+  }
+  void free() {
+    for (; !held_.empty(); held_.pop_back()) H().hsa_amd_memory_pool_free(held_.back());
+  }
+  // everything held, in allocation order; this set owns nothing afterwards
+  std::vector<void*> release() { return std::exchange(held_, {}); }
+
+  hsa_status_t status = HSA_STATUS_SUCCESS;
+  const char* what = "";
+
+ private:
+  bool step(hsa_status_t st, const char* label) {
+    if (ok() && st != HSA_STATUS_SUCCESS) {
+      status = st;
+      what = label;
+    }
+    return ok();
+  }
+  std::vector<void*> held_;
 };
 
 // The queue and executable a chip sweep or throughput check runs on. With kept
@@ -139,7 +182,7 @@ struct KernelSym {
 // is held meanwhile, so no probe packet interleaves. Otherwise a private queue
 // and executable are created for the check and destroyed after it.
 struct DeviceWork {
-  explicit DeviceWork(const Agent& a) : ag(a) {}
+  DeviceWork() = default;
   DeviceWork(const DeviceWork&) = delete;
   DeviceWork& operator=(const DeviceWork&) = delete;
   ~DeviceWork() {
@@ -150,7 +193,8 @@ struct DeviceWork {
   }
   bool borrowed() const { return slot != nullptr; }
 
-  hsa_status_t open(int ordinal, const char** what) {
+  hsa_status_t open(const Agent& agent, int ordinal, const char** what) {
+    ag = &agent;
     bool keep;
     {
       std::lock_guard<std::mutex> lk(g_resident_mu);
@@ -162,7 +206,7 @@ struct DeviceWork {
       if (!s->ready && !s->pending && !s->blocker) {
         mi355x_probe_result scratch;
         std::memset(&scratch, 0, sizeof(scratch));
-        if (setup_resources(ag, s->r, s->k, &scratch))
+        if (setup_resources(agent, s->r, s->k, &scratch))
           s->ready = true;
         else
           s->r.release();
@@ -182,10 +226,10 @@ struct DeviceWork {
       if ((st = H().hsa_executable_create_alt(HSA_PROFILE_FULL, HSA_DEFAULT_FLOAT_ROUNDING_MODE_DEFAULT, nullptr,
                                               &exe)) != 0)
         return *what = "executable create", st;
-      if ((st = H().hsa_executable_load_agent_code_object(exe, ag.agent, reader, nullptr, nullptr)) != 0)
+      if ((st = H().hsa_executable_load_agent_code_object(exe, agent.agent, reader, nullptr, nullptr)) != 0)
         return *what = "load code object", st;
       if ((st = H().hsa_executable_freeze(exe, nullptr)) != 0) return *what = "freeze", st;
-      if ((st = H().hsa_queue_create(ag.agent, 64, HSA_QUEUE_TYPE_SINGLE, nullptr, nullptr, UINT32_MAX, UINT32_MAX,
+      if ((st = H().hsa_queue_create(agent.agent, 64, HSA_QUEUE_TYPE_SINGLE, nullptr, nullptr, UINT32_MAX, UINT32_MAX,
                                      &queue)) != 0)
         return *what = "queue create", st;
       H().hsa_amd_profiling_set_profiler_enabled(queue, 1);
@@ -194,9 +238,9 @@ struct DeviceWork {
     return st;
   }
 
-  hsa_status_t symbol(const char* name, KernelSym* k) {
+  hsa_status_t symbol(const char* name, KernelInfo* k) {
     hsa_executable_symbol_t sym{};
-    const hsa_status_t st = H().hsa_executable_get_symbol_by_name(exe, name, &ag.agent, &sym);
+    const hsa_status_t st = H().hsa_executable_get_symbol_by_name(exe, name, &ag->agent, &sym);
     if (st != HSA_STATUS_SUCCESS) return st;
     H().hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_OBJECT, &k->kobj);
     H().hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_KERNARG_SEGMENT_SIZE, &k->kseg);
@@ -205,7 +249,7 @@ struct DeviceWork {
     return st;
   }
 
-  void submit(const KernelSym& k, void* kargs, uint32_t wgs, uint32_t wg_threads) {
+  void submit(const KernelInfo& k, void* kargs, uint32_t wgs, uint32_t wg_threads) {
     submit_kernel(queue, k.kobj, k.gseg, k.pseg, kargs, wgs, wg_threads, sig->s);
   }
 
@@ -213,7 +257,7 @@ struct DeviceWork {
   // write goes to the in-flight registry (at most one per device: later sweeps
   // and checks fail fast until it completes), and a borrowed kept queue blocks
   // probes until then.
-  void abandon(int ordinal, std::initializer_list<void*> bufs, std::chrono::steady_clock::time_point since) {
+  void abandon(int ordinal, Buffers& bufs, std::chrono::steady_clock::time_point since) {
     abandoned = true;
     SweepInFlight f;
     if (!borrowed()) {
@@ -222,13 +266,11 @@ struct DeviceWork {
       f.queue = queue;
     }
     f.sig = sig;
-    int i = 0;
-    for (void* b : bufs)
-      if (i < 6) f.bufs[i++] = b;
+    f.bufs = bufs.release();
     f.since = since;
     {
       std::lock_guard<std::mutex> lk(g_sweep_mu);
-      g_sweep_in_flight.emplace_back(ordinal, f);
+      g_sweep_in_flight.emplace_back(ordinal, std::move(f));
     }
     if (borrowed()) {
       slot->blocker = sig;
@@ -236,7 +278,7 @@ struct DeviceWork {
     }
   }
 
-  const Agent& ag;
+  const Agent* ag = nullptr;
   Resident* slot = nullptr;
   std::unique_lock<std::timed_mutex> slot_lk;
   hsa_code_object_reader_t reader{};
@@ -246,98 +288,136 @@ struct DeviceWork {
   bool abandoned = false;
 };
 
-void set_hsa_error(int* err, char* buf, size_t n, hsa_status_t st, const char* what) {
-  *err = static_cast<int>(st);
-  const char* msg = nullptr;
-  H().hsa_status_string(st, &msg);
-  std::snprintf(buf, n, "%s: %s", what, msg ? msg : "hsa error");
-}
+struct KernelSpec {
+  const char* symbol;
+  size_t args_bytes;  // what the host writes: the code object's kernarg segment must hold it
+};
 
+// What the checks have in common, over their result types (which share field
+// names, not layout): begin() up to the kernels' symbols, run() for one timed
+// dispatch, finish() / fail() for the return value. Where begin() or run()
+// return false, `out` holds the error and the check returns 1.
+template <typename R>
+struct Check {
+  using clk = std::chrono::steady_clock;
+
+  Check(int ordinal, double timeout_s, R* out) : ordinal(ordinal), timeout_s(timeout_s), out(out) {}
+
+  // `needs_device_memory`: the check allocates from the agent's own pool.
+  // `grid` is the result field for the workgroup count, `wgs_per_cu` per CU.
+  // `ks` receives one KernelInfo per spec; `kind` names the check in the
+  // kernarg-segment message.
+  bool begin(bool needs_device_memory, int R::*grid, uint32_t wgs_per_cu, const char* kind,
+             std::initializer_list<KernelSpec> specs, KernelInfo* ks) {
+    const int n = mi355x_hsa_probe_init();
+    if (n < 0) {
+      out->hsa_error = n;
+      std::snprintf(out->error, sizeof(out->error), "hsa_init: %.140s", H().loaded ? "runtime init failed" : H().error);
+      return false;
+    }
+    if (ordinal < 0 || ordinal >= n) {
+      std::snprintf(out->error, sizeof(out->error), "no such GPU agent (count=%d)", n);
+      return false;
+    }
+    if (const double s = in_flight_for(ordinal); s > 0) {
+      out->in_flight_s = s;
+      out->hsa_error = -1;
+      std::snprintf(out->error, sizeof(out->error),
+                    "earlier chip sweep / check still in flight for %.1fs (not completed)", s);
+      return finish(), false;
+    }
+    ag = &g_rt.gpus[ordinal];
+    uint32_t cus = 0, xcc = 0;
+    H().hsa_agent_get_info(ag->agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT), &cus);
+    H().hsa_agent_get_info(ag->agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_NUM_XCC), &xcc);
+    out->cu_count = static_cast<int>(cus);
+    out->num_xcc = static_cast<int>(xcc);
+    if (cus == 0 || cus > 1024 || !g_rt.has_fine || !g_rt.has_kernarg || (needs_device_memory && !ag->has_coarse)) {
+      std::snprintf(out->error, sizeof(out->error), "unexpected agent (cus=%u) or missing memory pool", cus);
+      return false;
+    }
+    out->*grid = static_cast<int>(cus * wgs_per_cu);
+
+    const char* what = "";
+    hsa_status_t s = dw.open(*ag, ordinal, &what);
+    if (s != HSA_STATUS_SUCCESS) return fail(s, what), false;
+    out->kept_queue = dw.borrowed() ? 1 : 0;
+    std::string segs;
+    bool fits = true;
+    for (const KernelSpec& spec : specs) {
+      if ((s = dw.symbol(spec.symbol, ks)) != HSA_STATUS_SUCCESS) return fail(s, "kernel symbol"), false;
+      segs += (segs.empty() ? "" : "/") + std::to_string(ks->kseg);
+      fits = fits && ks->kseg >= spec.args_bytes && ks->kseg <= kKernargBytes;
+      ++ks;
+    }
+    if (!fits) {
+      std::snprintf(out->error, sizeof(out->error), "%s kernarg segment%s %s: code object / host ABI mismatch", kind,
+                    specs.size() > 1 ? "s" : "", segs.c_str());
+      return finish(), false;
+    }
+    return true;
+  }
+
+  // One dispatch on the check's queue, waited for. Past the deadline, the
+  // dispatch and everything it may still write are abandoned to the in-flight
+  // registry and `out` says which stage it was.
+  bool run(const KernelInfo& k, void* kargs, uint32_t wgs, uint32_t wg_threads, const char* stage, double* us) {
+    dw.submit(k, kargs, wgs, wg_threads);
+    if (!wait_signal(dw.sig->s, timeout_s)) {
+      std::snprintf(out->error, sizeof(out->error), "%s did not complete within %.1fs", stage, timeout_s);
+      out->hsa_error = -1;
+      dw.abandon(ordinal, bufs, t0);
+      return finish(), false;
+    }
+    *us = dispatch_us(*ag, dw.sig->s);
+    return true;
+  }
+
+  // the buffers go before the clock stops; a private queue and executable after it
+  int finish() {
+    bufs.free();
+    out->total_us = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
+    return out->ok ? 0 : 1;
+  }
+  int fail(hsa_status_t s, const char* what) {
+    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, what);
+    return finish();
+  }
+
+  const int ordinal;
+  const double timeout_s;
+  R* const out;
+  const clk::time_point t0 = clk::now();
+  const Agent* ag = nullptr;
+  DeviceWork dw;
+  Buffers bufs;  // after dw: freed before a private queue and executable are destroyed
+};
+
+std::atomic<uint64_t> g_perf_poison{~0ull};
+// --corrupt-datapath: stage < 0 = off
+std::mutex g_dp_corrupt_mu;
+int g_dp_corrupt[4] = {-1, 0, 0, -1};  // stage, word, bit, ordinal
+
+}  // namespace
 }  // namespace mi355x::hsa_rt
 
 extern "C" int mi355x_hsa_chip_sweep(int ordinal, uint32_t nonce, int iters, double timeout_s,
                                      mi355x_sweep_result* out) {
-  using clk = std::chrono::steady_clock;
-  std::memset(out, 0, sizeof(*out));
-  out->ordinal = ordinal;
-  out->nonce = nonce;
+  *out = mi355x::blank_result<mi355x_sweep_result>(ordinal, nonce);
   out->iters = iters < 1 ? 1 : (iters > 64 ? 64 : iters);
-  const auto t0 = clk::now();
-  auto finish = [&] {
-    out->total_us = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-    return out->ok ? 0 : 1;
-  };
-  const int n = mi355x_hsa_probe_init();
-  if (n < 0) {
-    out->hsa_error = n;
-    std::snprintf(out->error, sizeof(out->error), "hsa_init: %.140s", H().loaded ? "runtime init failed" : H().error);
+  Check<mi355x_sweep_result> c(ordinal, timeout_s, out);
+  KernelInfo k;
+  if (!c.begin(true, &mi355x_sweep_result::grid, 1, "sweep", {{"mi355x_chip_sweep.kd", sizeof(mi355x_sweep_args)}}, &k))
     return 1;
-  }
-  if (ordinal < 0 || ordinal >= n) {
-    std::snprintf(out->error, sizeof(out->error), "no such GPU agent (count=%d)", n);
-    return 1;
-  }
-  if (sweep_still_in_flight(ordinal, out)) return finish();
-  const Agent& ag = g_rt.gpus[ordinal];
-  uint32_t cus = 0, xcc = 0;
-  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT), &cus);
-  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_NUM_XCC), &xcc);
-  out->cu_count = static_cast<int>(cus);
-  out->num_xcc = static_cast<int>(xcc);
-  if (cus == 0 || cus > 1024 || !g_rt.has_fine || !g_rt.has_kernarg || !ag.has_coarse) {
-    std::snprintf(out->error, sizeof(out->error), "unexpected agent (cus=%u) or missing memory pool", cus);
-    return 1;
-  }
-  const uint32_t grid = cus;
-  out->grid = static_cast<int>(grid);
-
-  DeviceWork dw(ag);
-  const char* what = "";
-  hsa_status_t s = dw.open(ordinal, &what);
-  if (s != HSA_STATUS_SUCCESS) {
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, what);
-    return finish();
-  }
-  out->kept_queue = dw.borrowed() ? 1 : 0;
-  KernelSym ksym;
-  if ((s = dw.symbol("mi355x_chip_sweep.kd", &ksym)) != HSA_STATUS_SUCCESS) {
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, "kernel symbol");
-    return finish();
-  }
-  if (ksym.kseg < sizeof(mi355x_sweep_args) || ksym.kseg > kKernargBytes) {
-    std::snprintf(out->error, sizeof(out->error), "sweep kernarg segment %u: code object / host ABI mismatch", ksym.kseg);
-    return finish();
-  }
-  uint32_t* records = nullptr;
-  float* tiles = nullptr;
-  uint32_t* arrive = nullptr;
-  mi355x_sweep_args* kargs = nullptr;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
   const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_SWEEP_REC_WORDS * sizeof(uint32_t);
   const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_PROBE_OUT * sizeof(float);
-  auto free_bufs = [&] {
-    if (kargs) H().hsa_amd_memory_pool_free(kargs);
-    if (arrive) H().hsa_amd_memory_pool_free(arrive);
-    if (tiles) H().hsa_amd_memory_pool_free(tiles);
-    if (records) H().hsa_amd_memory_pool_free(records);
-  };
-#define SWEEP_CHECK(expr, label)                                                              \
-  if ((s = (expr)) != HSA_STATUS_SUCCESS) {                                                   \
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, label);                 \
-    free_bufs();                                                                              \
-    return finish();                                                                          \
-  }
-  SWEEP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, rec_bytes, 0, reinterpret_cast<void**>(&records)),
-              "alloc records");
-  SWEEP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, tile_bytes, 0, reinterpret_cast<void**>(&tiles)),
-              "alloc tiles");
-  SWEEP_CHECK(H().hsa_amd_memory_pool_allocate(ag.coarse, 4096, 0, reinterpret_cast<void**>(&arrive)), "alloc arrive");
-  SWEEP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.kernarg, kKernargBytes, 0, reinterpret_cast<void**>(&kargs)),
-              "alloc kernarg");
-  SWEEP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, records), "allow records");
-  SWEEP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, tiles), "allow tiles");
-  SWEEP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, kargs), "allow kernarg");
-  SWEEP_CHECK(H().hsa_amd_memory_fill(arrive, 0u, 4096 / 4), "zero arrive");
-#undef SWEEP_CHECK
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.alloc<float>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  auto* arrive = c.bufs.alloc<uint32_t>(c.ag->coarse, 4096, "alloc arrive");
+  auto* kargs = c.bufs.alloc<mi355x_sweep_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  c.bufs.fill(arrive, 0u, 4096 / 4, "zero arrive");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
   std::memset(records, 0, rec_bytes);
   std::memset(tiles, 0xFF, tile_bytes);
   std::memset(kargs, 0, kKernargBytes);
@@ -348,179 +428,78 @@ extern "C" int mi355x_hsa_chip_sweep(int ordinal, uint32_t nonce, int iters, dou
   kargs->iters = out->iters;
   kargs->grid = grid;
   kargs->wait_ticks = 2000000;  // 20 ms at the 100 MHz s_memrealtime clock
-  dw.submit(ksym, kargs, grid, MI355X_SWEEP_THREADS);
-  if (!wait_signal(dw.sig->s, timeout_s)) {
-    std::snprintf(out->error, sizeof(out->error), "chip sweep did not complete within %.1fs", timeout_s);
-    out->hsa_error = -1;
-    dw.abandon(ordinal, {kargs, arrive, tiles, records}, t0);
-    return finish();
-  }
-  out->kernel_us = dispatch_us(ag, dw.sig->s);
+  if (!c.run(k, kargs, grid, MI355X_SWEEP_THREADS, "chip sweep", &out->kernel_us)) return 1;
   mi355x::sweep_verdict(records, tiles, grid, out);
-  free_bufs();
-  return finish();
+  return c.finish();
 }
-
-namespace mi355x::hsa_rt {
-std::atomic<uint64_t> g_perf_poison{~0ull};
-}  // namespace mi355x::hsa_rt
 
 extern "C" void mi355x_hsa_perf_poison(uint64_t unit) { g_perf_poison.store(unit, std::memory_order_relaxed); }
 
 extern "C" int mi355x_hsa_perf_check(int ordinal, uint32_t nonce, uint64_t bytes, int mfma_iters, double timeout_s,
                                      mi355x_perf_result* out) {
-  using clk = std::chrono::steady_clock;
-  std::memset(out, 0, sizeof(*out));
-  out->ordinal = ordinal;
-  out->nonce = nonce;
-  out->hbm_first_bad = -1;
+  *out = mi355x::blank_result<mi355x_perf_result>(ordinal, nonce);
+  out->hbm_first_bad = -1;  // a check that ran: no bad unit seen (a reply that never got here keeps 0)
   // 16-byte units, at least one full grid-stride round, at most 64 GiB
   bytes = bytes < (64ull << 20) ? (64ull << 20) : (bytes > (64ull << 30) ? (64ull << 30) : bytes);
   bytes &= ~static_cast<uint64_t>(0xFFFFF);
   out->bytes = bytes;
   out->mfma_iters = mfma_iters < 1 ? 1 : (mfma_iters > (1 << 22) ? (1 << 22) : mfma_iters);
-  const auto t0 = clk::now();
-  auto finish = [&] {
-    out->total_us = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-    return out->ok ? 0 : 1;
-  };
-  const int n = mi355x_hsa_probe_init();
-  if (n < 0) {
-    out->hsa_error = n;
-    std::snprintf(out->error, sizeof(out->error), "hsa_init: %.140s", H().loaded ? "runtime init failed" : H().error);
+  Check<mi355x_perf_result> c(ordinal, timeout_s, out);
+  KernelInfo ks[3];  // fill, check, burn
+  if (!c.begin(true, &mi355x_perf_result::mfma_grid, MI355X_BURN_WGS_PER_CU, "perf",
+               {{"mi355x_hbm_fill.kd", sizeof(mi355x_hbm_args)},
+                {"mi355x_hbm_check.kd", sizeof(mi355x_hbm_args)},
+                {"mi355x_mfma_burn.kd", sizeof(mi355x_burn_args)}},
+               ks))
     return 1;
-  }
-  if (ordinal < 0 || ordinal >= n) {
-    std::snprintf(out->error, sizeof(out->error), "no such GPU agent (count=%d)", n);
-    return 1;
-  }
-  if (sweep_still_in_flight(ordinal, out)) return finish();
-  const Agent& ag = g_rt.gpus[ordinal];
-  uint32_t cus = 0, xcc = 0;
-  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT), &cus);
-  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_NUM_XCC), &xcc);
-  out->cu_count = static_cast<int>(cus);
-  out->num_xcc = static_cast<int>(xcc);
-  if (cus == 0 || cus > 1024 || !g_rt.has_fine || !g_rt.has_kernarg || !ag.has_coarse) {
-    std::snprintf(out->error, sizeof(out->error), "unexpected agent (cus=%u) or missing memory pool", cus);
-    return 1;
-  }
+  const uint32_t cus = static_cast<uint32_t>(out->cu_count);
   const uint32_t fill_wgs = cus * MI355X_HBM_FILL_WGS_PER_CU;
   const uint32_t check_wgs = cus * MI355X_HBM_CHECK_WGS_PER_CU;
-  const uint32_t burn_wgs = cus * MI355X_BURN_WGS_PER_CU;
-  out->mfma_grid = static_cast<int>(burn_wgs);
-
-  DeviceWork w(ag);
-  const char* what = "";
-  hsa_status_t s = w.open(ordinal, &what);
-  if (s != HSA_STATUS_SUCCESS) {
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, what);
-    return finish();
-  }
-  out->kept_queue = w.borrowed() ? 1 : 0;
-  KernelSym ks[3];
-  const char* names[3] = {"mi355x_hbm_fill.kd", "mi355x_hbm_check.kd", "mi355x_mfma_burn.kd"};
-  for (int i = 0; i < 3; ++i)
-    if ((s = w.symbol(names[i], &ks[i])) != HSA_STATUS_SUCCESS) {
-      set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, "kernel symbol");
-      return finish();
-    }
-  if (ks[0].kseg < sizeof(mi355x_hbm_args) || ks[0].kseg > kKernargBytes || ks[1].kseg < sizeof(mi355x_hbm_args) ||
-      ks[1].kseg > kKernargBytes || ks[2].kseg < sizeof(mi355x_burn_args) || ks[2].kseg > kKernargBytes) {
-    std::snprintf(out->error, sizeof(out->error), "perf kernarg segments %u/%u/%u: code object / host ABI mismatch",
-                  ks[0].kseg, ks[1].kseg, ks[2].kseg);
-    return finish();
-  }
-  uint32_t* buf = nullptr;       // device, `bytes`
-  uint32_t* counters = nullptr;  // device, [0] bad words, [2..3] first bad unit
-  uint32_t* h_counters = nullptr;
-  uint32_t* records = nullptr;   // host-visible, burn_wgs records
-  char* kargs = nullptr;         // 3 slots of kKernargBytes
+  const uint32_t burn_wgs = static_cast<uint32_t>(out->mfma_grid);
   const size_t rec_bytes = static_cast<size_t>(burn_wgs) * MI355X_PERF_REC_WORDS * sizeof(uint32_t);
-  auto free_bufs = [&] {
-    if (kargs) H().hsa_amd_memory_pool_free(kargs);
-    if (records) H().hsa_amd_memory_pool_free(records);
-    if (h_counters) H().hsa_amd_memory_pool_free(h_counters);
-    if (counters) H().hsa_amd_memory_pool_free(counters);
-    if (buf) H().hsa_amd_memory_pool_free(buf);
-  };
-  auto abandon = [&](const char* stage) {
-    std::snprintf(out->error, sizeof(out->error), "%s did not complete within %.1fs", stage, timeout_s);
-    out->hsa_error = -1;
-    w.abandon(ordinal, {kargs, buf, counters, h_counters, records}, t0);
-    return finish();
-  };
-#define PERF_CHECK(expr, label)                                                               \
-  if ((s = (expr)) != HSA_STATUS_SUCCESS) {                                                   \
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, label);                 \
-    free_bufs();                                                                              \
-    return finish();                                                                          \
-  }
-  PERF_CHECK(H().hsa_amd_memory_pool_allocate(ag.coarse, bytes, 0, reinterpret_cast<void**>(&buf)), "alloc HBM buffer");
-  PERF_CHECK(H().hsa_amd_memory_pool_allocate(ag.coarse, 4096, 0, reinterpret_cast<void**>(&counters)),
-             "alloc counters");
-  PERF_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, 4096, 0, reinterpret_cast<void**>(&h_counters)),
-             "alloc host counters");
-  PERF_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, rec_bytes, 0, reinterpret_cast<void**>(&records)),
-             "alloc records");
-  PERF_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.kernarg, 4 * kKernargBytes, 0, reinterpret_cast<void**>(&kargs)),
-             "alloc kernarg");
-  PERF_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, h_counters), "allow counters");
-  PERF_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, records), "allow records");
-  PERF_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, kargs), "allow kernarg");
-  // counters: word 0 = 0 (bad words), words 2..3 = all ones (first bad unit)
-  PERF_CHECK(H().hsa_amd_memory_fill(counters, 0u, 2), "zero counters");
-  PERF_CHECK(H().hsa_amd_memory_fill(counters + 2, 0xFFFFFFFFu, 2), "init first-bad");
+  auto* buf = c.bufs.alloc<uint32_t>(c.ag->coarse, bytes, "alloc HBM buffer");
+  // device, [0] bad words, [1] bad words of the second pass, [2..3] first bad unit
+  auto* counters = c.bufs.alloc<uint32_t>(c.ag->coarse, 4096, "alloc counters");
+  auto* h_counters = c.bufs.alloc<uint32_t>(g_rt.fine, 4096, "alloc host counters", c.ag, "allow counters");
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  // 4 slots of kKernargBytes: fill, check, burn, second check
+  auto* kargs = c.bufs.alloc<char>(g_rt.kernarg, 4 * kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  c.bufs.fill(counters, 0u, 2, "zero counters");
+  c.bufs.fill(counters + 2, 0xFFFFFFFFu, 2, "init first-bad");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
   std::memset(h_counters, mi355x::kPerfCounterFillByte, 16);   // overwritten by the burn kernel's copy
   std::memset(records, 0, rec_bytes);
   std::memset(kargs, 0, 4 * kKernargBytes);
-  {
-    auto* fa = reinterpret_cast<mi355x_hbm_args*>(kargs);
-    auto* ca = reinterpret_cast<mi355x_hbm_args*>(kargs + kKernargBytes);
-    auto* ba = reinterpret_cast<mi355x_burn_args*>(kargs + 2 * kKernargBytes);
-    auto* c2 = reinterpret_cast<mi355x_hbm_args*>(kargs + 3 * kKernargBytes);
-    fa->buf = ca->buf = buf;
-    fa->n16 = ca->n16 = bytes / 16;
-    fa->bad = ca->bad = counters;
-    fa->first_bad = ca->first_bad = reinterpret_cast<uint64_t*>(counters + 2);
-    fa->threads = static_cast<uint64_t>(fill_wgs) * MI355X_PERF_THREADS;
-    ca->threads = static_cast<uint64_t>(check_wgs) * MI355X_PERF_THREADS;
-    fa->poison_unit = g_perf_poison.load(std::memory_order_relaxed);
-    ca->poison_unit = ~0ull;
-    fa->seed = ca->seed = nonce * 0x01000193u + 0x7F4A7C15u;
-    *c2 = *ca;
-    c2->bad = counters + 1;  // the second read pass counts on its own
-    ba->records = records;
-    ba->hbm_counters = counters;
-    ba->hbm_counters_host = h_counters;
-    ba->nonce = nonce;
-    ba->iters = out->mfma_iters;
-  }
-  w.submit(ks[0], kargs, fill_wgs, MI355X_PERF_THREADS);
-  if (!wait_signal(w.sig->s, timeout_s)) return abandon("HBM fill");
-  out->fill_us = dispatch_us(ag, w.sig->s);
-  w.submit(ks[1], kargs + kKernargBytes, check_wgs, MI355X_PERF_THREADS);
-  if (!wait_signal(w.sig->s, timeout_s)) return abandon("HBM check");
-  out->check_us = dispatch_us(ag, w.sig->s);
-  // a second read pass: steady-state read bandwidth (the first one still
-  // competes with the fill's write-back) and a second look at every word
-  w.submit(ks[1], kargs + 3 * kKernargBytes, check_wgs, MI355X_PERF_THREADS);
-  if (!wait_signal(w.sig->s, timeout_s)) return abandon("HBM check (2nd pass)");
-  out->check2_us = dispatch_us(ag, w.sig->s);
-  w.submit(ks[2], kargs + 2 * kKernargBytes, burn_wgs, MI355X_PERF_THREADS);
-  if (!wait_signal(w.sig->s, timeout_s)) return abandon("MFMA burn");
-  out->mfma_us = dispatch_us(ag, w.sig->s);
-#undef PERF_CHECK
+  auto* fa = reinterpret_cast<mi355x_hbm_args*>(kargs);
+  auto* ca = reinterpret_cast<mi355x_hbm_args*>(kargs + kKernargBytes);
+  auto* ba = reinterpret_cast<mi355x_burn_args*>(kargs + 2 * kKernargBytes);
+  auto* c2 = reinterpret_cast<mi355x_hbm_args*>(kargs + 3 * kKernargBytes);
+  fa->buf = ca->buf = buf;
+  fa->n16 = ca->n16 = bytes / 16;
+  fa->bad = ca->bad = counters;
+  fa->first_bad = ca->first_bad = reinterpret_cast<uint64_t*>(counters + 2);
+  fa->threads = static_cast<uint64_t>(fill_wgs) * MI355X_PERF_THREADS;
+  ca->threads = static_cast<uint64_t>(check_wgs) * MI355X_PERF_THREADS;
+  fa->poison_unit = g_perf_poison.load(std::memory_order_relaxed);
+  ca->poison_unit = ~0ull;
+  fa->seed = ca->seed = nonce * 0x01000193u + 0x7F4A7C15u;
+  *c2 = *ca;
+  c2->bad = counters + 1;  // the second read pass counts on its own
+  ba->records = records;
+  ba->hbm_counters = counters;
+  ba->hbm_counters_host = h_counters;
+  ba->nonce = nonce;
+  ba->iters = out->mfma_iters;
+  // two read passes: the second one gives steady-state read bandwidth (the
+  // first still competes with the fill's write-back) and a second look at every word
+  if (!c.run(ks[0], fa, fill_wgs, MI355X_PERF_THREADS, "HBM fill", &out->fill_us) ||
+      !c.run(ks[1], ca, check_wgs, MI355X_PERF_THREADS, "HBM check", &out->check_us) ||
+      !c.run(ks[1], c2, check_wgs, MI355X_PERF_THREADS, "HBM check (2nd pass)", &out->check2_us) ||
+      !c.run(ks[2], ba, burn_wgs, MI355X_PERF_THREADS, "MFMA burn", &out->mfma_us))
+    return 1;
   mi355x::perf_verdict(records, h_counters, burn_wgs, out);
-  free_bufs();
-  return finish();
+  return c.finish();
 }
-
-namespace mi355x::hsa_rt {
-// --corrupt-datapath: stage < 0 = off
-std::mutex g_dp_corrupt_mu;
-int g_dp_corrupt[4] = {-1, 0, 0, -1};  // stage, word, bit, ordinal
-}  // namespace mi355x::hsa_rt
 
 extern "C" void mi355x_hsa_datapath_corrupt(int stage, int word, int bit, int ordinal) {
   std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
@@ -531,84 +510,20 @@ extern "C" void mi355x_hsa_datapath_corrupt(int stage, int word, int bit, int or
 }
 
 extern "C" int mi355x_hsa_datapath_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_result* out) {
-  using clk = std::chrono::steady_clock;
-  std::memset(out, 0, sizeof(*out));
-  out->ordinal = ordinal;
-  out->nonce = nonce;
-  out->first_bad_wg = out->first_bad_stage = out->first_bad_word = -1;
-  const auto t0 = clk::now();
-  auto finish = [&] {
-    out->total_us = std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-    return out->ok ? 0 : 1;
-  };
-  const int n = mi355x_hsa_probe_init();
-  if (n < 0) {
-    out->hsa_error = n;
-    std::snprintf(out->error, sizeof(out->error), "hsa_init: %.140s", H().loaded ? "runtime init failed" : H().error);
+  *out = mi355x::blank_result<mi355x_datapath_result>(ordinal, nonce);
+  Check<mi355x_datapath_result> c(ordinal, timeout_s, out);
+  KernelInfo k;
+  // no device memory: records, tiles and kernargs all live in host pools
+  if (!c.begin(false, &mi355x_datapath_result::grid, 1, "datapath",
+               {{"mi355x_mfma_datapath.kd", sizeof(mi355x_datapath_args)}}, &k))
     return 1;
-  }
-  if (ordinal < 0 || ordinal >= n) {
-    std::snprintf(out->error, sizeof(out->error), "no such GPU agent (count=%d)", n);
-    return 1;
-  }
-  if (sweep_still_in_flight(ordinal, out)) return finish();
-  const Agent& ag = g_rt.gpus[ordinal];
-  uint32_t cus = 0, xcc = 0;
-  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT), &cus);
-  H().hsa_agent_get_info(ag.agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_NUM_XCC), &xcc);
-  out->cu_count = static_cast<int>(cus);
-  out->num_xcc = static_cast<int>(xcc);
-  if (cus == 0 || cus > 1024 || !g_rt.has_fine || !g_rt.has_kernarg) {
-    std::snprintf(out->error, sizeof(out->error), "unexpected agent (cus=%u) or missing memory pool", cus);
-    return 1;
-  }
-  const uint32_t grid = cus;
-  out->grid = static_cast<int>(grid);
-
-  DeviceWork dw(ag);
-  const char* what = "";
-  hsa_status_t s = dw.open(ordinal, &what);
-  if (s != HSA_STATUS_SUCCESS) {
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, what);
-    return finish();
-  }
-  out->kept_queue = dw.borrowed() ? 1 : 0;
-  KernelSym ksym;
-  if ((s = dw.symbol("mi355x_mfma_datapath.kd", &ksym)) != HSA_STATUS_SUCCESS) {
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, "kernel symbol");
-    return finish();
-  }
-  if (ksym.kseg < sizeof(mi355x_datapath_args) || ksym.kseg > kKernargBytes) {
-    std::snprintf(out->error, sizeof(out->error), "datapath kernarg segment %u: code object / host ABI mismatch",
-                  ksym.kseg);
-    return finish();
-  }
-  uint32_t* records = nullptr;
-  uint32_t* tiles = nullptr;
-  mi355x_datapath_args* kargs = nullptr;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
   const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DP_REC_WORDS * sizeof(uint32_t);
   const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DP_WG_WORDS * sizeof(uint32_t);
-  auto free_bufs = [&] {
-    if (kargs) H().hsa_amd_memory_pool_free(kargs);
-    if (tiles) H().hsa_amd_memory_pool_free(tiles);
-    if (records) H().hsa_amd_memory_pool_free(records);
-  };
-#define DP_CHECK(expr, label)                                                                 \
-  if ((s = (expr)) != HSA_STATUS_SUCCESS) {                                                   \
-    set_hsa_error(&out->hsa_error, out->error, sizeof(out->error), s, label);                 \
-    free_bufs();                                                                              \
-    return finish();                                                                          \
-  }
-  DP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, rec_bytes, 0, reinterpret_cast<void**>(&records)),
-           "alloc records");
-  DP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.fine, tile_bytes, 0, reinterpret_cast<void**>(&tiles)),
-           "alloc tiles");
-  DP_CHECK(H().hsa_amd_memory_pool_allocate(g_rt.kernarg, kKernargBytes, 0, reinterpret_cast<void**>(&kargs)),
-           "alloc kernarg");
-  DP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, records), "allow records");
-  DP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, tiles), "allow tiles");
-  DP_CHECK(H().hsa_amd_agents_allow_access(1, &ag.agent, nullptr, kargs), "allow kernarg");
-#undef DP_CHECK
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  auto* kargs = c.bufs.alloc<mi355x_datapath_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
   std::memset(records, 0, rec_bytes);
   std::memset(tiles, 0xFF, tile_bytes);
   std::memset(kargs, 0, kKernargBytes);
@@ -616,22 +531,14 @@ extern "C" int mi355x_hsa_datapath_check(int ordinal, uint32_t nonce, double tim
   kargs->tiles = tiles;
   kargs->nonce = nonce;
   kargs->grid = grid;
-  dw.submit(ksym, kargs, grid, MI355X_DP_THREADS);
-  if (!wait_signal(dw.sig->s, timeout_s)) {
-    std::snprintf(out->error, sizeof(out->error), "datapath check did not complete within %.1fs", timeout_s);
-    out->hsa_error = -1;
-    dw.abandon(ordinal, {kargs, tiles, records}, t0);
-    return finish();
-  }
-  out->kernel_us = dispatch_us(ag, dw.sig->s);
+  if (!c.run(k, kargs, grid, MI355X_DP_THREADS, "datapath check", &out->kernel_us)) return 1;
   {
     std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* c = g_dp_corrupt;
-    if (c[0] >= 0 && c[0] < MI355X_DP_STAGES && c[1] >= 0 && c[1] < MI355X_DP_TILE && c[2] >= 0 && c[2] < 32 &&
-        (c[3] < 0 || c[3] == ordinal))
-      tiles[c[0] * MI355X_DP_TILE + c[1]] ^= 1u << c[2];
+    const int* cr = g_dp_corrupt;
+    if (cr[0] >= 0 && cr[0] < MI355X_DP_STAGES && cr[1] >= 0 && cr[1] < MI355X_DP_TILE && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      tiles[cr[0] * MI355X_DP_TILE + cr[1]] ^= 1u << cr[2];
   }
   mi355x::datapath_verdict(records, tiles, grid, out);
-  free_bufs();
-  return finish();
+  return c.finish();
 }

@@ -1,7 +1,8 @@
 // ROCr state shared by the HSA-direct probe's translation units:
 // hsa_probe.cpp (runtime start-up, the liveness probe, kept per-device
 // queues), hsa_peer.cpp (the xGMI peer copy check) and hsa_chip.cpp (the
-// full-chip sweep and the throughput check). Internal to src/health.
+// full-chip sweep, the throughput check and the MFMA datapath check).
+// Internal to src/health.
 #pragma once
 
 #include <hsa/hsa.h>

@@ -1,12 +1,14 @@
-// The JSON objects the probe prints for a chip sweep and a throughput check
-// (shared by probe_main.cpp and native/tests/kernel_contract_cli.cpp, so a test
-// sees exactly the line the prober parses). Strings grow as needed: a long
+// The JSON objects the probe prints for a chip sweep, a throughput check and a
+// datapath check (shared by probe_main.cpp and the contract CLIs under
+// native/tests, so a test sees exactly the line the prober parses), and the
+// blank result each of them starts from. Strings grow as needed: a long
 // escaped `error` next to wide numbers is never cut.
 #pragma once
 
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "mi355x/liveness_probe.h"
 
@@ -41,6 +43,20 @@ __attribute__((format(printf, 1, 2))) inline std::string json_format(const char*
   if (n > 0) std::vsnprintf(&o[0], o.size() + 1, fmt, ap2);
   va_end(ap2);
   return o;
+}
+
+// The result of a check on `ordinal` before anything is known: all zero but
+// what the type defines otherwise -- the datapath result's first_bad_* = -1
+// ("none"). hbm_first_bad of the throughput result stays 0 here: a reply that
+// never reached the runtime carries 0, mi355x_hsa_perf_check sets its own -1.
+template <typename R>
+R blank_result(int ordinal, uint32_t nonce) {
+  R r{};
+  r.ordinal = ordinal;
+  r.nonce = nonce;
+  if constexpr (std::is_same_v<R, mi355x_datapath_result>)
+    r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
+  return r;
 }
 
 inline std::string sweep_json(const mi355x_sweep_result& r) {

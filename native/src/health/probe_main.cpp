@@ -70,6 +70,7 @@ uint64_t mono_ns() {
   return static_cast<uint64_t>(ts.tv_sec) * 1000000000ull + ts.tv_nsec;
 }
 
+using mi355x::blank_result;
 using mi355x::datapath_json;
 using mi355x::json_escape;
 using mi355x::perf_json;
@@ -145,41 +146,36 @@ int probe(int o, uint32_t nonce, int iters, double, mi355x_probe_result* r) {
   return mi355x_probe_device(o, nonce, iters, r);
 }
 int identify_dev(int o, mi355x_probe_result* r) { return mi355x_probe_identify(o, r); }
-int chip_sweep(int o, uint32_t nonce, int iters, double, mi355x_sweep_result* r) {
-  std::memset(r, 0, sizeof(*r));
-  r->ordinal = o;
-  r->nonce = nonce;
-  r->iters = iters;
-  std::snprintf(r->error, sizeof(r->error), "--sweep needs the HSA-direct build (mi355x-liveness-probe)");
+// the checks this build does not have: `blank` with the reason, status 1
+template <typename R>
+int needs_hsa_build(const char* flag, const R& blank, R* r) {
+  *r = blank;
+  std::snprintf(r->error, sizeof(r->error), "%s needs the HSA-direct build (mi355x-liveness-probe)", flag);
   return 1;
+}
+int chip_sweep(int o, uint32_t nonce, int iters, double, mi355x_sweep_result* r) {
+  auto blank = blank_result<mi355x_sweep_result>(o, nonce);
+  blank.iters = iters;
+  return needs_hsa_build("--sweep", blank, r);
 }
 void perf_poison(uint64_t) {}
 void datapath_corrupt(int, int, int, int) {}
 int datapath_check(int o, uint32_t nonce, double, mi355x_datapath_result* r) {
-  std::memset(r, 0, sizeof(*r));
-  r->ordinal = o;
-  r->nonce = nonce;
-  r->first_bad_wg = r->first_bad_stage = r->first_bad_word = -1;
-  std::snprintf(r->error, sizeof(r->error), "--datapath needs the HSA-direct build (mi355x-liveness-probe)");
-  return 1;
+  return needs_hsa_build("--datapath", blank_result<mi355x_datapath_result>(o, nonce), r);
 }
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
-  std::memset(r, 0, sizeof(*r));
-  r->ordinal = o;
-  r->nonce = nonce;
-  r->bytes = bytes;
-  r->mfma_iters = iters;
-  std::snprintf(r->error, sizeof(r->error), "--perf needs the HSA-direct build (mi355x-liveness-probe)");
-  return 1;
+  auto blank = blank_result<mi355x_perf_result>(o, nonce);
+  blank.bytes = bytes;
+  blank.mfma_iters = iters;
+  return needs_hsa_build("--perf", blank, r);
 }
 int peer(int a, int b, uint32_t, uint64_t bytes, int reps, double, mi355x_peer_result* r) {
-  std::memset(r, 0, sizeof(*r));
-  r->src = a;
-  r->dst = b;
-  r->bytes = bytes;
-  r->reps = reps;
-  std::snprintf(r->error, sizeof(r->error), "--peer needs the HSA-direct build (mi355x-liveness-probe)");
-  return 1;
+  mi355x_peer_result blank{};
+  blank.src = a;
+  blank.dst = b;
+  blank.bytes = bytes;
+  blank.reps = reps;
+  return needs_hsa_build("--peer", blank, r);
 }
 #endif
 
@@ -289,19 +285,22 @@ int run_peer(const std::vector<int>& ords, uint32_t nonce, uint64_t bytes, int r
   return all_ok ? 0 : 1;
 }
 
-// --sweep: the full-chip sweep on each selected GPU (parallel host threads).
-bool run_sweeps(const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
-                const std::vector<double>& timeouts, int n, std::string& json) {
-  std::vector<mi355x_sweep_result> res(ords.size());
+// A whole-chip check on each selected GPU, one host thread per GPU (every GPU
+// has its own CUs, HBM and matrix cores): `call` runs it on one device,
+// `to_json` prints that device's result. `json` becomes the reply's "devices"
+// array; true when every device passed.
+template <typename R, typename Call>
+bool run_on_each(const std::vector<int>& ords, const std::vector<uint32_t>& nonces, const std::vector<double>& timeouts,
+                 int n, Call call, std::string (*to_json)(const R&), std::string& json) {
+  std::vector<R> res(ords.size());
   std::vector<int> rcs(ords.size(), 1);
   auto one = [&](size_t i) {
     if (ords[i] < 0 || ords[i] >= n) {
-      std::memset(&res[i], 0, sizeof(res[i]));
-      res[i].ordinal = ords[i];
+      res[i] = blank_result<R>(ords[i], 0);  // this reply carries no nonce
       std::snprintf(res[i].error, sizeof(res[i].error), "no such GPU (count=%d)", n);
       return;
     }
-    rcs[i] = chip_sweep(ords[i], nonces[i], iters, timeouts[i], &res[i]);
+    rcs[i] = call(ords[i], nonces[i], timeouts[i], &res[i]);
   };
   std::vector<std::thread> ths;
   for (size_t i = 0; i < ords.size(); ++i) ths.emplace_back(one, i);
@@ -311,68 +310,28 @@ bool run_sweeps(const std::vector<int>& ords, const std::vector<uint32_t>& nonce
   for (size_t i = 0; i < res.size(); ++i) {
     ok = ok && rcs[i] == 0;
     if (i) json += ",";
-    json += sweep_json(res[i]);
+    json += to_json(res[i]);
   }
   json += "]";
   return ok;
 }
 
-// --perf: the throughput check on each selected GPU (parallel host threads;
-// every GPU has its own HBM and matrix cores).
-bool run_perf(const std::vector<int>& ords, const std::vector<uint32_t>& nonces, uint64_t bytes, int iters,
-              const std::vector<double>& timeouts, int n, std::string& json) {
-  std::vector<mi355x_perf_result> res(ords.size());
-  std::vector<int> rcs(ords.size(), 1);
-  auto one = [&](size_t i) {
-    if (ords[i] < 0 || ords[i] >= n) {
-      std::memset(&res[i], 0, sizeof(res[i]));
-      res[i].ordinal = ords[i];
-      std::snprintf(res[i].error, sizeof(res[i].error), "no such GPU (count=%d)", n);
-      return;
-    }
-    rcs[i] = perf_check(ords[i], nonces[i], bytes, iters, timeouts[i], &res[i]);
-  };
-  std::vector<std::thread> ths;
-  for (size_t i = 0; i < ords.size(); ++i) ths.emplace_back(one, i);
-  for (auto& t : ths) t.join();
-  bool ok = !ords.empty();
-  json = "[";
-  for (size_t i = 0; i < res.size(); ++i) {
-    ok = ok && rcs[i] == 0;
-    if (i) json += ",";
-    json += perf_json(res[i]);
-  }
-  json += "]";
-  return ok;
-}
-
-// --datapath: the MFMA datapath check on each selected GPU (parallel host threads).
-bool run_datapath(const std::vector<int>& ords, const std::vector<uint32_t>& nonces,
-                  const std::vector<double>& timeouts, int n, std::string& json) {
-  std::vector<mi355x_datapath_result> res(ords.size());
-  std::vector<int> rcs(ords.size(), 1);
-  auto one = [&](size_t i) {
-    if (ords[i] < 0 || ords[i] >= n) {
-      std::memset(&res[i], 0, sizeof(res[i]));
-      res[i].ordinal = ords[i];
-      res[i].first_bad_wg = res[i].first_bad_stage = res[i].first_bad_word = -1;
-      std::snprintf(res[i].error, sizeof(res[i].error), "no such GPU (count=%d)", n);
-      return;
-    }
-    rcs[i] = datapath_check(ords[i], nonces[i], timeouts[i], &res[i]);
-  };
-  std::vector<std::thread> ths;
-  for (size_t i = 0; i < ords.size(); ++i) ths.emplace_back(one, i);
-  for (auto& t : ths) t.join();
-  bool ok = !ords.empty();
-  json = "[";
-  for (size_t i = 0; i < res.size(); ++i) {
-    ok = ok && rcs[i] == 0;
-    if (i) json += ",";
-    json += datapath_json(res[i]);
-  }
-  json += "]";
-  return ok;
+// --sweep / --perf / --datapath and the server's requests of those kinds.
+// `iters`: the sweep's tile iterations or the throughput check's MFMA
+// iterations; `bytes`: the throughput check's HBM buffer.
+bool run_check(const std::string& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
+               uint64_t bytes, const std::vector<double>& timeouts, int n, std::string& json) {
+  if (kind == "sweep")
+    return run_on_each(ords, nonces, timeouts, n, [=](int o, uint32_t nonce, double t, mi355x_sweep_result* r) {
+      return chip_sweep(o, nonce, iters, t, r);
+    }, sweep_json, json);
+  if (kind == "perf")
+    return run_on_each(ords, nonces, timeouts, n, [=](int o, uint32_t nonce, double t, mi355x_perf_result* r) {
+      return perf_check(o, nonce, bytes, iters, t, r);
+    }, perf_json, json);
+  return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_result* r) {
+    return datapath_check(o, nonce, t, r);
+  }, datapath_json, json);
 }
 
 // "S:W:B" or "S:W:B@O" of --corrupt-datapath
@@ -502,12 +461,8 @@ void answer(const ServeRequest& r, int n) {
   defer_teardown();
   std::string body;
   bool ok;
-  if (r.kind == "sweep") {
-    ok = run_sweeps(r.ords, r.nonces, r.iters, r.timeouts, n, body);
-  } else if (r.kind == "perf") {
-    ok = run_perf(r.ords, r.nonces, static_cast<uint64_t>(r.perf_mib) << 20, r.iters, r.timeouts, n, body);
-  } else if (r.kind == "datapath") {
-    ok = run_datapath(r.ords, r.nonces, r.timeouts, n, body);
+  if (r.kind != "probe") {
+    ok = run_check(r.kind, r.ords, r.nonces, r.iters, static_cast<uint64_t>(r.perf_mib) << 20, r.timeouts, n, body);
   } else {
     std::vector<mi355x_probe_result> results;
     ok = run_batch(r.ords, r.nonces, r.iters, r.timeouts, false, n, results);
@@ -755,32 +710,13 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> nonces;
   for (size_t i = 0; i < ords.size(); ++i) nonces.push_back(nonce + static_cast<uint32_t>(i));
   const std::vector<double> timeouts(ords.size(), timeout_s);
-  if (perf_mode) {
+  if (perf_mode || datapath_mode || sweep_mode) {
+    const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : "sweep";
     std::string body;
-    const bool ok = run_perf(ords, nonces, perf_mib << 20, perf_iters, timeouts, n, body);
-    std::printf("{\"ok\":%s,\"perf\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
+    const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
+    std::printf("{\"ok\":%s,\"%s\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
                 "\"t_ready_ns\":%llu,\"devices\":%s}\n",
-                ok ? "true" : "false", n, static_cast<unsigned long long>(t_start),
-                static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(mono_ns()), body.c_str());
-    std::fflush(stdout);
-    return ok ? 0 : 1;
-  }
-  if (datapath_mode) {
-    std::string body;
-    const bool ok = run_datapath(ords, nonces, timeouts, n, body);
-    std::printf("{\"ok\":%s,\"datapath\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
-                "\"t_ready_ns\":%llu,\"devices\":%s}\n",
-                ok ? "true" : "false", n, static_cast<unsigned long long>(t_start),
-                static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(mono_ns()), body.c_str());
-    std::fflush(stdout);
-    return ok ? 0 : 1;
-  }
-  if (sweep_mode) {
-    std::string body;
-    const bool ok = run_sweeps(ords, nonces, iters, timeouts, n, body);
-    std::printf("{\"ok\":%s,\"sweep\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
-                "\"t_ready_ns\":%llu,\"devices\":%s}\n",
-                ok ? "true" : "false", n, static_cast<unsigned long long>(t_start),
+                ok ? "true" : "false", kind, n, static_cast<unsigned long long>(t_start),
                 static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(mono_ns()), body.c_str());
     std::fflush(stdout);
     return ok ? 0 : 1;

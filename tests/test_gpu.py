@@ -937,6 +937,66 @@ def test_check_past_its_deadline_on_the_kept_queue(ordinals):
             p.wait()
 
 
+_CHECK_FLAGS = {
+    "sweep": ["--sweep", "--iters", "1"],
+    "perf": ["--perf", "--perf-mib", "64", "--perf-iters", "1024"],     # 64 MiB: the smallest buffer accepted
+    "datapath": ["--datapath"],
+}
+# what a reply that never reached a device must leave at zero
+_CHECK_COUNTERS = {
+    "sweep": ["hsa_error", "iters", "grid", "cu_count", "num_xcc", "records_ok", "mfma_bad", "lds_bad",
+              "tile_bad", "cus_covered", "xccs_covered", "kernel_us", "arrival_spread_us", "total_us", "in_flight_s"],
+    "perf": ["hsa_error", "bytes", "cu_count", "num_xcc", "fill_us", "check_us", "check2_us",
+             "hbm_write_gbps", "hbm_read_gbps", "hbm_bad_words", "hbm_bad_words_pass2", "hbm_first_bad", "mfma_iters",
+             "mfma_grid", "mfma_records_ok", "mfma_checksum_mismatch", "mfma_xccs", "mfma_us", "mfma_tflops",
+             "clock_mhz_min", "clock_mhz_median", "clock_mhz_max", "total_us", "in_flight_s"],
+    "datapath": ["hsa_error", "grid", "cu_count", "num_xcc", "records_ok", "mfma_bad", "tile_bad",
+                 "first_bad_got", "first_bad_want", "first_bad_xor", "cus_covered", "simds_covered", "xccs_covered",
+                 "kernel_us", "total_us", "in_flight_s"],
+}
+
+
+def _one_shot_check(runtime, kind, devices, nonce, ordinals):
+    from rocm_k8s_device_plugin_amd.ops.native import probe_executable
+    env = dict(os.environ, ROCR_VISIBLE_DEVICES=str(sorted(ordinals.values())[0]))
+    p = subprocess.run([str(probe_executable(runtime)), *_CHECK_FLAGS[kind], "--devices", devices, "--nonce",
+                        str(nonce), "--timeout", "20"], stdout=subprocess.PIPE, env=env, timeout=120)
+    return p.returncode, json.loads(p.stdout.decode().strip().splitlines()[-1])
+
+
+@pytest.mark.parametrize("kind", ["sweep", "perf", "datapath"])
+def test_check_replies_for_a_missing_gpu_and_a_missing_backend(kind, ordinals):
+    """The replies of the whole-chip checks that never reach a device: an
+    ordinal past the visible GPUs next to one that runs (HSA build), and the
+    HIP build, which has none of these checks."""
+    rc, doc = _one_shot_check("hsa", kind, "0,99", 7000, ordinals)
+    assert rc == 1 and doc["ok"] is False and doc[kind] is True and doc["hip_device_count"] == 1, doc
+    good, missing = doc["devices"]
+    assert good["ok"] is True and good["ordinal"] == 0 and good["nonce"] == 7000, good
+    assert missing["ok"] is False and missing["ordinal"] == 99 and missing["kept_queue"] is False, missing
+    assert missing["error"] == "no such GPU (count=1)", missing
+    assert [k for k in _CHECK_COUNTERS[kind] if missing[k] != 0] == [], missing
+    if kind == "sweep":
+        assert set(missing["wgs_per_xcc"]) == {0} and missing["all_resident"] is False, missing
+    elif kind == "perf":
+        assert set(missing["xcd_clock_mhz"]) == {0}, missing
+    else:
+        assert missing["stage_bad"] == [0, 0, 0, 0], missing
+        assert missing["first_bad_wg"] == missing["first_bad_stage"] == missing["first_bad_word"] == -1, missing
+
+    rc, doc = _one_shot_check("hip", kind, "0", 7100, ordinals)
+    d = doc["devices"][0]
+    assert rc == 1 and doc["ok"] is False and d["ok"] is False and d["ordinal"] == 0 and d["nonce"] == 7100, doc
+    assert d["error"].endswith("needs the HSA-direct build (mi355x-liveness-probe)"), d
+    assert d["error"].startswith(f"--{kind} "), d
+    if kind == "sweep":
+        assert d["iters"] == 1, d
+    elif kind == "perf":
+        assert d["bytes"] == 64 << 20 and d["mfma_iters"] == 1024, d
+    else:
+        assert d["first_bad_wg"] == d["first_bad_stage"] == d["first_bad_word"] == -1, d
+
+
 def test_monitor_perf_check_on_idle_gpu(inv, ordinals):
     """The health monitor's cadence: liveness, then the throughput check on the
     idle GPU in the same sweep; a healthy MI355X clears every floor."""
