@@ -51,7 +51,22 @@ struct mi355x_datapath_args {
   uint32_t* tiles;    // host-visible, grid * MI355X_DP_WG_WORDS (wave 0's four tiles per workgroup)
   uint32_t nonce;
   uint32_t grid;      // workgroups launched; a workgroup beyond it writes nothing
+#if defined(MI355X_TEST_INJECT)
+  // Test-only build (liveness_gfx950_inject.hsaco; no shipped binary loads it):
+  // one wrong accumulator word after a stage's MFMA, before the comparison and
+  // the tile store, so the tests can see ctr[stage] fire. Runtime arguments; an
+  // index outside 0..63 does nothing. The fields mirror mi355x_sweep_args'.
+  uint32_t inject_kind;   // MI355X_DP_INJECT_*
+  uint32_t inject_wg;
+  uint32_t inject_wave;   // 0..3
+  uint32_t inject_lane;   // 0..63
+  uint32_t inject_index;  // stage * 16 + accumulator register
+  uint32_t inject_mask;   // xor-ed into that word
+#endif
 };
+
+#define MI355X_DP_INJECT_NONE 0
+#define MI355X_DP_INJECT_MFMA 1
 
 #if defined(__HIPCC__)
 #define MI355X_DP_HD __host__ __device__ inline

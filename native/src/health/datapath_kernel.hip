@@ -46,6 +46,15 @@ extern "C" __global__ __launch_bounds__(MI355X_DP_THREADS) void mi355x_mfma_data
 #pragma unroll
     for (uint32_t r = 0; r < 16; ++r) acc[r] = dp_as_float(dp_c_word(stage, (r & 3) + 8 * (r >> 2) + 4 * kk, col, nw));
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+#if defined(MI355X_TEST_INJECT)
+    {
+      const bool hit = args.inject_kind == MI355X_DP_INJECT_MFMA && wg == args.inject_wg &&
+                       wave == args.inject_wave && lane == args.inject_lane;
+#pragma unroll
+      for (uint32_t r = 0; r < 16; ++r)
+        if (hit && stage * 16 + r == args.inject_index) acc[r] = dp_as_float(dp_as_word(acc[r]) ^ args.inject_mask);
+    }
+#endif
     uint32_t bad = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 16; ++r) {

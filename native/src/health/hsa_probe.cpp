@@ -499,7 +499,7 @@ extern "C" int mi355x_hsa_probe_device(int ordinal, uint32_t nonce, int iters, d
   std::memset(out, 0, sizeof(*out));
   out->kfd_node_id = -1;
   out->nonce = nonce;
-  out->iters = iters < 1 ? 1 : iters;
+  out->iters = probe_clamp_iters(iters);
   const auto t0 = clk::now();
   auto finish = [&] {
     out->total_us = std::chrono::duration<double, std::micro>(clk::now() - t0).count();

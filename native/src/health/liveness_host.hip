@@ -118,7 +118,7 @@ extern "C" int mi355x_probe_device(int ordinal, uint32_t nonce, int iters, mi355
   std::memset(out, 0, sizeof(*out));
   out->ordinal = ordinal;
   out->nonce = nonce;
-  out->iters = iters < 1 ? 1 : iters;
+  out->iters = probe_clamp_iters(iters);
   const auto t0 = std::chrono::steady_clock::now();
   auto t_setup = t0;
   float* h_out = nullptr;

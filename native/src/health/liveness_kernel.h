@@ -42,6 +42,23 @@ MI355X_HD float probe_a(int i, int k, uint32_t nonce) { return (float)((int)((i 
 MI355X_HD float probe_b(int k, int j, uint32_t nonce) { return (float)((int)((j * 11u + k * 2u + nonce) % 5u) - 2); }
 MI355X_HD float probe_c(int i, int j, uint32_t nonce) { return (float)((int)((i + 2u * j + nonce) % 4u)); }
 
+// The tile is exact only while every partial sum c + m * (A·B), and the sum
+// after the first of an iteration's two products, is an integer fp32 holds
+// exactly. The generators give c in 0..3, a in -3..3, b in -2..2, so |A·B| <= 12;
+// of the 174 (c, a0*b0, a1*b1) triples they can produce together, (1, 6, 6) grows
+// fastest towards an odd number: 1 + 12 * m <= 2^24 holds up to m = 1398101, and
+// 1 + 12 * 1398102 = 16777225 is odd and above 2^24, where fp32 holds only even
+// integers. Past that the host's c + float(iters) * dot and the matrix unit's
+// accumulation may round differently, and a healthy GPU would be reported
+// unhealthy. ((1, 6, 6) is the only triple with |A·B| = 12 and needs a nonce
+// within 343 of 2^32, where i*3u + k*5u + nonce wraps for some indices and not
+// for others; tests/test_iteration_bound.py enumerates all triples.) Every entry
+// point that takes an iteration count clamps it into 1..MI355X_PROBE_MAX_ITERS.
+#define MI355X_PROBE_MAX_ITERS 1398101
+MI355X_HD int probe_clamp_iters(int iters) {
+  return iters < 1 ? 1 : (iters > MI355X_PROBE_MAX_ITERS ? MI355X_PROBE_MAX_ITERS : iters);
+}
+
 // ---- full-chip sweep (mi355x_chip_sweep) --------------------------------------
 // One 256-lane workgroup per CU: each holds all 160 KiB of its CU's LDS, so no
 // two workgroups can share a CU, and they wait (bounded) until the whole grid
@@ -75,7 +92,23 @@ struct mi355x_sweep_args {
   int32_t iters;
   uint32_t grid;       // workgroups launched (= CUs of the agent)
   uint32_t wait_ticks; // max residency wait, s_memrealtime ticks
+#if defined(MI355X_TEST_INJECT)
+  // Test-only build (liveness_gfx950_inject.hsaco; no shipped binary loads it):
+  // one wrong data word, so the tests can see the device-side comparators fire.
+  // Runtime arguments: nothing folds at compile time. An index outside the
+  // accumulator (16 registers) or the LDS pattern does nothing.
+  uint32_t inject_kind;   // MI355X_INJECT_*
+  uint32_t inject_wg;     // workgroup
+  uint32_t inject_wave;   // mfma: wave 0..3 of that workgroup
+  uint32_t inject_lane;   // mfma: lane 0..63 of that wave
+  uint32_t inject_index;  // mfma: accumulator register 0..15 after the last MFMA; lds: pattern word
+  uint32_t inject_mask;   // xor-ed into that word
+#endif
 };
+
+#define MI355X_INJECT_NONE 0
+#define MI355X_INJECT_MFMA 1  // a wrong matrix result: before the comparison and the tile store
+#define MI355X_INJECT_LDS 2   // a bad LDS cell: after the pattern is written, before the barrier
 
 MI355X_HD uint32_t sweep_nonce(uint32_t nonce, uint32_t wg, uint32_t wave) { return nonce + wg * 4u + wave; }
 MI355X_HD uint32_t sweep_lds_pattern(uint32_t i, uint32_t nonce, uint32_t wg) {

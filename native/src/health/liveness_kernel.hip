@@ -20,6 +20,10 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The bit pattern of a float passed by value. (__builtin_bit_cast applied directly to a vector
+// element, `acc[r]`, reads the vector's first element whatever r is.)
+__device__ inline uint32_t f32_word(float f) { return __builtin_bit_cast(uint32_t, f); }
+
 // s_getreg_b32 HW_REG_XCC_ID (hwreg 20 on gfx94x/gfx950), bits [3:0].
 #define MI355X_HWREG_XCC_ID ((20) | (0 << 6) | ((16 - 1) << 11))
 // HW_REG_HW_ID (hwreg 4): wave/simd/cu/se ids, for the record.
@@ -98,6 +102,16 @@ extern "C" __global__ __launch_bounds__(MI355X_SWEEP_THREADS) void mi355x_chip_s
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = probe_c((r & 3) + 8 * (r >> 2) + 4 * kk, row, n);
   for (int it = 0; it < args.iters; ++it) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+#if defined(MI355X_TEST_INJECT)
+  {
+    const bool hit = args.inject_kind == MI355X_INJECT_MFMA && wg == args.inject_wg && wave == args.inject_wave &&
+                     static_cast<uint32_t>(lane) == args.inject_lane;
+#pragma unroll
+    for (uint32_t r = 0; r < 16; ++r)
+      if (hit && r == args.inject_index)
+        acc[r] = __builtin_bit_cast(float, f32_word(acc[r]) ^ args.inject_mask);
+  }
+#endif
   uint32_t bad = 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -105,7 +119,8 @@ extern "C" __global__ __launch_bounds__(MI355X_SWEEP_THREADS) void mi355x_chip_s
     float dot = 0.f;
     for (int k = 0; k < MI355X_PROBE_K; ++k) dot += probe_a(i, k, n) * probe_b(k, row, n);
     const float want = probe_c(i, row, n) + static_cast<float>(args.iters) * dot;
-    bad += acc[r] != want;
+    // words, not values (probe_verify.h): -0.0 == 0.0, so a flipped sign bit of a zero element would pass
+    bad += f32_word(acc[r]) != f32_word(want);
   }
   if (bad) atomicAdd(&ctr[0], bad);
   if (wave == 0) {
@@ -117,6 +132,12 @@ extern "C" __global__ __launch_bounds__(MI355X_SWEEP_THREADS) void mi355x_chip_s
   // whole-LDS pattern, read back from another wave's writes
   for (uint32_t i = tid; i < MI355X_SWEEP_LDS_WORDS; i += MI355X_SWEEP_THREADS)
     lds[i] = sweep_lds_pattern(i, args.nonce, wg);
+#if defined(MI355X_TEST_INJECT)
+  // the thread that wrote the word spoils it, so no other thread's write is raced
+  if (args.inject_kind == MI355X_INJECT_LDS && wg == args.inject_wg && args.inject_index < MI355X_SWEEP_LDS_WORDS &&
+      args.inject_index % MI355X_SWEEP_THREADS == tid)
+    lds[args.inject_index] ^= args.inject_mask;
+#endif
   __syncthreads();
   uint32_t lbad = 0;
   const uint32_t other = (tid + 64) & (MI355X_SWEEP_THREADS - 1);

@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "../kube/json.h"
+#include "liveness_kernel.h"
 #include "mi355x/dp_service.h"
 #include "mi355x/glog.h"
 #include "mi355x/metrics.h"
@@ -316,7 +317,9 @@ struct LivenessProber::Server {
   }
 };
 
-LivenessProber::LivenessProber(ProberConfig cfg) : cfg_(std::move(cfg)) {}
+// -liveness_iters (daemon) / probe_iters (binding): past the bound the liveness
+// tile is no longer exact and a healthy GPU could fail its probe
+LivenessProber::LivenessProber(ProberConfig cfg) : cfg_(std::move(cfg)) { cfg_.iters = probe_clamp_iters(cfg_.iters); }
 LivenessProber::~LivenessProber() { close(); }
 
 bool LivenessProber::server_running() const {

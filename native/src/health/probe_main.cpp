@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "init_sampler.h"
+#include "liveness_kernel.h"
 #include "mi355x/liveness_probe.h"
 #include "probe_json.h"
 
@@ -221,6 +222,7 @@ void refresh_fault_injection() {
 bool run_batch(const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
                const std::vector<double>& timeouts, bool identify, int n, std::vector<mi355x_probe_result>& results) {
   results.assign(ords.size(), mi355x_probe_result{});
+  iters = probe_clamp_iters(iters);  // --iters and serve's "probe <iters>": the tile is exact up to the bound only
   std::vector<int> rcs(ords.size(), 1);
   auto run_one = [&](size_t i) {
     if (ords[i] < 0 || ords[i] >= n) {

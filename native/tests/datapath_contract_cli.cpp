@@ -5,6 +5,9 @@
 //   datapath_contract_cli gen     < requests    one unsigned word per request line:
 //        a stage i k nw | b stage k j nw | c stage i j nw | wave_nonce nonce wg wave
 //   datapath_contract_cli layout                "struct field offset" / "struct sizeof n" / "define NAME n" lines
+//   datapath_contract_cli inject-layout         "define NAME n" lines of the injection contract and, when compiled
+//        with -DMI355X_TEST_INJECT=1 (as the test-only code object is), mi355x_datapath_args with its
+//        trailing injection fields
 //   datapath_contract_cli verdict < cases       datapath_json lines of mi355x::datapath_verdict. A case:
 //        uint32 grid, nonce, variants; grid*16 record words; grid*4096 tile words; then per variant:
 //        uint32 n and n patches (uint32 array, index, value), array 0 = records, 1 = tiles. One line
@@ -67,6 +70,25 @@ static int cmd_layout() {
   DEFINE(MI355X_DPREC_XCC);
   DEFINE(MI355X_DPREC_HWID);
   DEFINE(MI355X_DPREC_BAD);
+  return 0;
+}
+
+static int cmd_inject_layout() {
+#if defined(MI355X_TEST_INJECT)
+  FIELD(mi355x_datapath_args, records);
+  FIELD(mi355x_datapath_args, tiles);
+  FIELD(mi355x_datapath_args, nonce);
+  FIELD(mi355x_datapath_args, grid);
+  FIELD(mi355x_datapath_args, inject_kind);
+  FIELD(mi355x_datapath_args, inject_wg);
+  FIELD(mi355x_datapath_args, inject_wave);
+  FIELD(mi355x_datapath_args, inject_lane);
+  FIELD(mi355x_datapath_args, inject_index);
+  FIELD(mi355x_datapath_args, inject_mask);
+  SIZE(mi355x_datapath_args);
+#endif
+  DEFINE(MI355X_DP_INJECT_NONE);
+  DEFINE(MI355X_DP_INJECT_MFMA);
   return 0;
 }
 
@@ -143,7 +165,8 @@ int main(int argc, char** argv) {
   const std::string cmd = argc > 1 ? argv[1] : "";
   if (cmd == "gen") return cmd_gen();
   if (cmd == "layout") return cmd_layout();
+  if (cmd == "inject-layout") return cmd_inject_layout();
   if (cmd == "verdict") return cmd_verdict();
-  std::fprintf(stderr, "usage: %s gen|layout|verdict\n", argv[0]);
+  std::fprintf(stderr, "usage: %s gen|layout|inject-layout|verdict\n", argv[0]);
   return 2;
 }

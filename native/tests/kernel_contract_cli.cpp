@@ -9,6 +9,9 @@
 //        a i k nonce | b k j nonce | c i j nonce | sweep_nonce nonce wg wave |
 //        lds i nonce wg | hbm word seed | burn lane j nonce
 //   kernel_contract_cli layout                "struct field offset" / "struct sizeof n" lines
+//   kernel_contract_cli inject-layout         "define NAME n" lines of the iteration bound and the injection
+//        contract and, when compiled with -DMI355X_TEST_INJECT=1 (as the test-only code object is),
+//        mi355x_sweep_args with its trailing injection fields, as `layout` prints a struct
 //   kernel_contract_cli verify  < records     one "ok mismatches error" line per binary record:
 //        uint32 nonce, int32 iters, 1024 floats, 4 meta words
 //   kernel_contract_cli sweep-verdict < cases  sweep_json lines of mi355x::sweep_verdict. A case:
@@ -100,6 +103,34 @@ static int cmd_layout() {
   FIELD(mi355x_burn_args, nonce);
   FIELD(mi355x_burn_args, iters);
   SIZE(mi355x_burn_args);
+  return 0;
+}
+
+#define DEFINE(N) std::printf("define %s %llu\n", #N, static_cast<unsigned long long>(N))
+
+static int cmd_inject_layout() {
+#if defined(MI355X_TEST_INJECT)
+  FIELD(mi355x_sweep_args, records);
+  FIELD(mi355x_sweep_args, tiles);
+  FIELD(mi355x_sweep_args, arrive);
+  FIELD(mi355x_sweep_args, nonce);
+  FIELD(mi355x_sweep_args, iters);
+  FIELD(mi355x_sweep_args, grid);
+  FIELD(mi355x_sweep_args, wait_ticks);
+  FIELD(mi355x_sweep_args, inject_kind);
+  FIELD(mi355x_sweep_args, inject_wg);
+  FIELD(mi355x_sweep_args, inject_wave);
+  FIELD(mi355x_sweep_args, inject_lane);
+  FIELD(mi355x_sweep_args, inject_index);
+  FIELD(mi355x_sweep_args, inject_mask);
+  SIZE(mi355x_sweep_args);
+#endif
+  DEFINE(MI355X_PROBE_MAX_ITERS);
+  DEFINE(MI355X_SWEEP_THREADS);
+  DEFINE(MI355X_SWEEP_LDS_WORDS);
+  DEFINE(MI355X_INJECT_NONE);
+  DEFINE(MI355X_INJECT_MFMA);
+  DEFINE(MI355X_INJECT_LDS);
   return 0;
 }
 
@@ -303,10 +334,11 @@ int main(int argc, char** argv) {
   const std::string cmd = argc > 1 ? argv[1] : "";
   if (cmd == "gen") return cmd_gen();
   if (cmd == "layout") return cmd_layout();
+  if (cmd == "inject-layout") return cmd_inject_layout();
   if (cmd == "verify") return cmd_verify();
   if (cmd == "sweep-verdict") return cmd_sweep_verdict();
   if (cmd == "perf-verdict") return cmd_perf_verdict();
   if (cmd == "json") return cmd_json(argc, argv);
-  std::fprintf(stderr, "usage: %s gen|layout|verify|sweep-verdict|perf-verdict|json\n", argv[0]);
+  std::fprintf(stderr, "usage: %s gen|layout|inject-layout|verify|sweep-verdict|perf-verdict|json\n", argv[0]);
   return 2;
 }

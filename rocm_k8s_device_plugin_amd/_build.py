@@ -7,6 +7,8 @@ Outputs land inside the package so they travel with the repo snapshot:
 * ``bin/mi355x-liveness-probe``   HSA-direct probe executable (health loop, bench "container")
 * ``bin/mi355x-liveness-probe-hip`` the same probe through the HIP runtime
 * ``kernels/liveness_gfx950.hsaco``
+* ``kernels/liveness_gfx950_inject.hsaco`` the same kernels with the test injection hook
+  (MI355X_TEST_INJECT); only testing/raw_kernels.py loads it, nothing shipped contains it
 * ``bin/kernel_contract_cli``     host-only driver of the kernel contract and the sweep /
   throughput verdicts (testing/contract_cli.py)
 * ``bin/datapath_contract_cli``   the same for the MFMA datapath check (testing/datapath_reference.py)
@@ -35,6 +37,7 @@ PROBE_EXE_HIP = PKG_DIR / "bin" / "mi355x-liveness-probe-hip"
 MOUNTEMU_EXE = PKG_DIR / "bin" / "mi355x-probe-mountemu"
 HIP_DEVEMU_EXE = PKG_DIR / "bin" / "mi355x-probe-hip-devemu"
 HSACO = PKG_DIR / "kernels" / "liveness_gfx950.hsaco"
+HSACO_INJECT = PKG_DIR / "kernels" / "liveness_gfx950_inject.hsaco"
 CONTRACT_CLI = PKG_DIR / "bin" / "kernel_contract_cli"
 DATAPATH_CLI = PKG_DIR / "bin" / "datapath_contract_cli"
 
@@ -209,7 +212,7 @@ def ensure_built(hip: bool | None = None) -> None:
         hip = hipcc_available()
     if hip in _checked:
         return
-    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO] if hip else [])
+    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO, HSACO_INJECT] if hip else [])
     if not _up_to_date(targets, hip):
         BUILD_DIR.mkdir(parents=True, exist_ok=True)
         with open(BUILD_DIR.parent / ".build.lock", "w") as lk:

@@ -111,6 +111,11 @@ class _ProbeServer:
         await self.proc.wait()
 
 
+# MI355X_PROBE_MAX_ITERS (native/src/health/liveness_kernel.h): the most MFMA iterations at which
+# every partial sum of the liveness tile is an integer fp32 holds exactly
+PROBE_MAX_ITERS = 1398101
+
+
 class LivenessProber:
     MODES = ("persistent", "spawn")
     SERVER_BACKOFF_SWEEPS = 4
@@ -123,7 +128,8 @@ class LivenessProber:
             raise ValueError(f"liveness mode must be one of {self.MODES}, got {mode!r}")
         self.exe = str(exe) if exe else None
         self.timeout_s = timeout_s
-        self.iters = iters
+        # clamped like the native prober's: past the bound the tile is no longer exact
+        self.iters = min(max(1, int(iters)), PROBE_MAX_ITERS)
         self.max_parallel = max(1, max_parallel)
         self.extra_env = dict(extra_env or {})
         self.argv_prefix = list(argv_prefix)

@@ -244,23 +244,58 @@ def healthy(grid: int, nonce: int, placement=None):
     return recs, tiles_image(nonce, grid).copy()
 
 
+ACC_REGS = 16
+
+
+def accumulator_element(lane: int, reg: int) -> tuple:
+    """(row, column) of a stage's 32x32 tile that accumulator register `reg` of
+    lane `lane` holds: D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31]."""
+    assert 0 <= lane < 64 and 0 <= reg < ACC_REGS
+    return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), lane & 31
+
+
+def injection_image(nonce: int, grid: int, inject=None) -> tuple:
+    """(stage_bad (grid, 4), tiles (grid, 4, 32, 32) uint32) that
+    mi355x_mfma_datapath of the test-only build must leave behind under `inject`
+    (a raw_kernels request's "inject" object: index = stage * 16 + register;
+    None for the hook off), from the documented layout alone. The wrong word is
+    counted once, by its workgroup, in its stage's counter; it reaches the
+    host's tiles only from wave 0, and there it differs from the healthy word by
+    exactly the mask. An index outside 0..63 injects nothing."""
+    stage_bad = np.zeros((grid, STAGES), dtype=np.int64)
+    tiles = tiles_image(nonce, grid).copy()
+    if inject is not None and inject["mask"] & M32 and inject["wg"] < grid:
+        assert inject["kind"] == "mfma", inject
+        wg, wave, lane, index = inject["wg"], inject["wave"], inject["lane"], inject["index"]
+        if wave < WAVES and lane < 64 and index < STAGES * ACC_REGS:
+            stage, reg = divmod(index, ACC_REGS)
+            stage_bad[wg, stage] = 1
+            if wave == 0:
+                i, j = accumulator_element(lane, reg)
+                tiles[wg, stage, i, j] ^= np.uint32(inject["mask"] & M32)
+    return stage_bad, tiles
+
+
 HW_WORDS = (REC_XCC, REC_HWID, REC_HWID + 1, REC_HWID + 2, REC_HWID + 3)   # hardware's, not the reference's
 
 
-def check_raw(records, tiles, nonce: int, grid: int) -> None:
+def check_raw(records, tiles, nonce: int, grid: int, inject=None) -> None:
     """Every word the kernel wrote against the reference image: the whole tile
     buffer, and the records but for where the workgroup ran (those: XCC id in
-    range, HW_ID words non-zero)."""
+    range, HW_ID words non-zero). `inject`: the injection the test-only build
+    was asked for (injection_image)."""
     rec = np.asarray(records, dtype=np.uint32).reshape(grid, REC_WORDS)
     til = np.asarray(tiles, dtype=np.uint32).reshape(grid, STAGES, ROWS, COLS)
     want_rec, want_tiles = healthy(grid, nonce)
+    want_bad, want_tiles = injection_image(nonce, grid, inject)
+    want_rec[:, REC_BAD:REC_BAD + STAGES] = want_bad
     bad = np.argwhere(til != want_tiles)
     assert bad.size == 0, (f"nonce {nonce:#x} grid {grid}: {len(bad)} tile words differ, first (wg, stage, i, j) "
                            f"{tuple(bad[0])}: got {int(til[tuple(bad[0])]):#010x} want "
                            f"{int(want_tiles[tuple(bad[0])]):#010x}")
     keep = [w for w in range(REC_WORDS) if w not in HW_WORDS]
-    assert (rec[:, keep] == want_rec[:, keep]).all(), (nonce, grid, rec[:, keep].tolist())
-    assert (rec[:, REC_BAD:REC_BAD + STAGES] == 0).all(), rec[:, REC_BAD:REC_BAD + STAGES].tolist()
+    assert (rec[:, keep] == want_rec[:, keep]).all(), (nonce, grid, inject, rec[:, keep].tolist())
+    assert (rec[:, REC_BAD:REC_BAD + STAGES] == want_bad).all(), (inject, rec[:, REC_BAD:REC_BAD + STAGES].tolist())
     assert (rec[:, REC_XCC] < 16).all(), rec[:, REC_XCC].tolist()
     assert (rec[:, REC_HWID:REC_HWID + WAVES] != 0).all(), rec[:, REC_HWID:REC_HWID + WAVES].tolist()
 
@@ -350,6 +385,17 @@ def assert_verdict(got: dict, want: dict, what: str = "") -> None:
 RECORDS, TILES = 0, 1      # a patch's array
 
 
+def compile_cli(exe, extra_flags=()) -> Path:
+    from .contract_cli import host_compiler
+    cxx = host_compiler()
+    assert cxx, "no host C++ compiler"
+    cmd = [cxx, "-std=c++17", "-O1", *extra_flags]
+    for inc in CLI_INCLUDES:
+        cmd += ["-I", str(inc)]
+    subprocess.run(cmd + [str(CLI_SOURCE), "-o", str(exe)], check=True, timeout=300)
+    return Path(exe)
+
+
 def contract_cli(build_dir) -> Path:
     """The program the native build left in the package's bin directory when it
     was built from the sources as they are now, else one compiled into `build_dir`."""
@@ -358,14 +404,7 @@ def contract_cli(build_dir) -> Path:
     exe = _build.DATAPATH_CLI
     if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
         return exe
-    cxx = host_compiler()
-    assert cxx, "no host C++ compiler"
-    out = Path(build_dir) / "datapath_contract_cli"
-    cmd = [cxx, "-std=c++17", "-O1"]
-    for inc in CLI_INCLUDES:
-        cmd += ["-I", str(inc)]
-    subprocess.run(cmd + [str(CLI_SOURCE), "-o", str(out)], check=True, timeout=300)
-    return out
+    return compile_cli(Path(build_dir) / "datapath_contract_cli")
 
 
 def case(records, tiles, grid: int, nonce: int, variants=()) -> bytes:

@@ -111,6 +111,60 @@ def tile_f32(nonce: int, iters: int) -> np.ndarray:
     return t.astype(np.float32)
 
 
+# ---- how many iterations the tile stays exact for (MI355X_PROBE_MAX_ITERS) -----
+PROBE_MAX_ITERS = 1398101
+# Every nonce class there is: without a wrap the operands depend on nonce mod
+# lcm(4, 7, 5) = 140; the largest index term is 11*31 + 2 = 343, so each nonce
+# from 2^32 - 343 on wraps in its own set of terms and is listed itself.
+TRIPLE_NONCES = tuple(range(280)) + tuple(range((1 << 32) - 1024, 1 << 32))
+
+
+def operand_triples(nonces=TRIPLE_NONCES) -> dict:
+    """Every (c, a0*b0, a1*b1) an element of the tile can have, each with one
+    (nonce, i, j) that produces it. Integer arithmetic mod 2^32, like the header's."""
+    found = {}
+    i = np.arange(PROBE_M, dtype=np.uint64)[:, None]
+    j = np.arange(PROBE_N, dtype=np.uint64)[None, :]
+    m32 = np.uint64(M32)
+    for n in nonces:
+        n64 = np.uint64(n)
+        a = [(((i * np.uint64(3) + np.uint64(5 * k) + n64) & m32) % np.uint64(7)).astype(np.int64) - 3 for k in (0, 1)]
+        b = [(((j * np.uint64(11) + np.uint64(2 * k) + n64) & m32) % np.uint64(5)).astype(np.int64) - 2 for k in (0, 1)]
+        c = (((i + np.uint64(2) * j + n64) & m32) % np.uint64(4)).astype(np.int64)
+        packed = (c * 64 + (a[0] * b[0] + 8)) * 64 + (a[1] * b[1] + 8)      # products lie in -6..6
+        values, first = np.unique(packed.ravel(), return_index=True)
+        for v, at in zip(values.tolist(), first.tolist()):
+            found.setdefault((v // 4096, v // 64 % 64 - 8, v % 64 - 8), (n, at // PROBE_N, at % PROBE_N))
+    return found
+
+
+def fp32_holds(v: int) -> bool:
+    """Whether fp32 represents the integer v exactly (24 significant bits)."""
+    v = abs(v)
+    return v == 0 or (v >> ((v & -v).bit_length() - 1)).bit_length() <= 24
+
+
+def inexact_steps(triple, iters: int) -> list:
+    """The values of one element's computation over `iters` iterations that fp32
+    does not hold exactly: the accumulator after every product, with the two
+    products of an iteration in either order, and the host's float(iters) * dot
+    and c + float(iters) * dot. Each is linear in the iteration number, so its
+    magnitude is largest at an end, and the first iteration's values are tiny:
+    the iterations are walked from the last one down until all of one
+    iteration's values are at most 2^24 in magnitude; every value before that is
+    an integer below 2^24, which fp32 holds."""
+    c, p0, p1 = triple
+    dot = p0 + p1
+    assert max(abs(c), abs(c + p0), abs(c + p1), abs(c + dot)) < 1 << 24
+    bad = [v for v in (iters * dot, c + iters * dot) if not fp32_holds(v)]
+    for t in reversed(range(iters)):
+        values = (c + t * dot + p0, c + t * dot + p1, c + (t + 1) * dot)
+        if all(abs(v) <= 1 << 24 for v in values):
+            break
+        bad += [v for v in values if not fp32_holds(v)]
+    return bad
+
+
 def scratch_image(t: np.ndarray) -> np.ndarray:
     """The 16x64 float image the liveness kernel leaves in scratch: slot
     r*64+lane is accumulator register r of lane `lane`, which holds
@@ -223,9 +277,65 @@ def check_liveness(out, scratch, meta, nonce: int, iters: int) -> None:
     assert int(meta[META_XCC]) < NUM_XCC_MAX, f"meta xcc {int(meta[META_XCC])}"
 
 
-def check_sweep(records, tiles, nonce: int, iters: int, grid: int) -> None:
+SWEEP_WAVES = 4
+ACC_REGS = 16
+
+
+def accumulator_element(lane: int, reg: int) -> tuple:
+    """(row, column) of the 32x32 tile that accumulator register `reg` of lane
+    `lane` holds: D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31]."""
+    assert 0 <= lane < 64 and 0 <= reg < ACC_REGS
+    return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), lane & 31
+
+
+def sweep_wave_value(nonce: int, iters: int, wg: int, wave: int, lane: int, reg: int) -> int:
+    """The exact integer in accumulator register `reg` of lane `lane` of that wave."""
+    i, j = accumulator_element(lane, reg)
+    return int(tile(sweep_nonce(nonce, wg, wave), iters)[i, j])
+
+
+def sweep_injection_image(nonce: int, iters: int, grid: int, inject=None) -> dict:
+    """What mi355x_chip_sweep of the test-only build must leave behind under
+    `inject` (a raw_kernels request's "inject" object, or None for the hook
+    off), from the documented layout alone: "mfma_bad" and "lds_bad" per
+    workgroup, and "tiles" (grid, 32, 32) float32. A wrong word is counted once
+    by the workgroup it is in and by no other; it reaches the host's tile only
+    from wave 0, and there it differs from the healthy word by exactly the
+    mask. An index outside the accumulator or the LDS pattern injects nothing."""
+    mfma_bad, lds_bad = np.zeros(grid, dtype=np.int64), np.zeros(grid, dtype=np.int64)
+    tiles = sweep_tiles(nonce, iters, grid).copy()
+    if inject is not None and inject["mask"] & M32 and inject["wg"] < grid:
+        wg, index, mask = inject["wg"], inject["index"], inject["mask"] & M32
+        if inject["kind"] == "lds":
+            if index < SWEEP_LDS_WORDS:
+                lds_bad[wg] = 1
+        else:
+            assert inject["kind"] == "mfma", inject
+            wave, lane = inject["wave"], inject["lane"]
+            if wave < SWEEP_WAVES and lane < 64 and index < ACC_REGS:
+                mfma_bad[wg] = 1
+                if wave == 0:
+                    i, j = accumulator_element(lane, index)
+                    _bits(tiles)[wg, i, j] ^= np.uint32(mask)
+    return {"mfma_bad": mfma_bad, "lds_bad": lds_bad, "tiles": tiles}
+
+
+def check_sweep(records, tiles, nonce: int, iters: int, grid: int, inject=None) -> None:
+    """`inject`: the injection the test-only build was asked for (sweep_injection_image)."""
     records = np.asarray(records, dtype=np.uint32).reshape(grid, REC_WORDS)
     tiles = np.asarray(tiles, dtype=np.float32).reshape(grid, PROBE_M, PROBE_N)
+    if inject is not None:
+        want = sweep_injection_image(nonce, iters, grid, inject)
+        for wg in range(grid):
+            rec = [int(x) for x in records[wg]]
+            assert rec[REC_MAGIC] == SWEEP_MAGIC and rec[REC_WG] == wg and rec[REC_NONCE] == nonce ^ wg, (wg, rec)
+            assert rec[REC_MFMA_BAD] == want["mfma_bad"][wg], (
+                f"wg {wg}: mfma_bad {rec[REC_MFMA_BAD]}, want {int(want['mfma_bad'][wg])} under {inject}")
+            assert rec[REC_LDS_BAD] == want["lds_bad"][wg], (
+                f"wg {wg}: lds_bad {rec[REC_LDS_BAD]}, want {int(want['lds_bad'][wg])} under {inject}")
+            assert 1 <= rec[REC_ARRIVED] <= grid and rec[REC_XCC] < NUM_XCC_MAX, (wg, rec)
+            assert_bit_equal(tiles[wg], want["tiles"][wg], f"wg {wg} tile under {inject}")
+        return
     for wg in range(grid):
         rec = [int(x) for x in records[wg]]
         assert rec[REC_MAGIC] == SWEEP_MAGIC, f"wg {wg}: magic {rec[REC_MAGIC]:#x}"

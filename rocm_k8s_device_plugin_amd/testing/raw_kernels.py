@@ -14,9 +14,20 @@ REQUESTS.json is a list of requests, run in order:
     {"id": ..., "kernel": "burn", "nonce": n, "iters": k, "grid": g, "hbm_counters": [4 words]}
     {"id": ..., "kernel": "datapath", "nonce": n, "grid": g}
 
+A sweep or datapath request may add "code_object": "inject": the kernel then comes from
+liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
+the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h), and may add
+
+    "inject": {"kind": "mfma" | "lds", "wg": w, "wave": v, "lane": l, "index": i, "mask": m}
+
+(one data word xor-ed with m: accumulator register i of that lane after the last MFMA -- for the
+datapath i = stage * 16 + register -- or LDS pattern word i; wave and lane are unused for "lds").
+Without "inject" the hook is off. Every other request uses the production code object.
+
 For each request OUTDIR gets <id>.<buffer>.npy and <id>.<buffer>.canary.npy
 (2 x CANARY_BYTES: the guard before and after the buffer), and OUTDIR/status.json
-names the completed requests and the first error. The launcher stops at the
+names the completed requests, each one's launch-to-synchronize time ("launch_us", measured, never
+judged here) and the first error. The launcher stops at the
 first HIP error, or at any non-success from the synchronize after a kernel,
 writes what it has, and exits non-zero; it never retries.
 
@@ -32,6 +43,7 @@ import ctypes
 import json
 import os
 import sys
+import time
 from pathlib import Path
 
 import numpy as np
@@ -71,6 +83,49 @@ class DatapathArgs(ctypes.Structure):
 
 # the mirrors of datapath_kernel.h (native/tests/datapath_contract_cli.cpp prints that header's layout)
 DATAPATH_ARG_STRUCTS = {"mi355x_datapath_args": DatapathArgs}
+
+_INJECT_FIELDS = [("inject_kind", _u32), ("inject_wg", _u32), ("inject_wave", _u32), ("inject_lane", _u32),
+                  ("inject_index", _u32), ("inject_mask", _u32)]
+
+
+class SweepInjectArgs(ctypes.Structure):
+    _fields_ = SweepArgs._fields_ + _INJECT_FIELDS
+
+
+class DatapathInjectArgs(ctypes.Structure):
+    _fields_ = DatapathArgs._fields_ + _INJECT_FIELDS
+
+
+# the same structs as the test-only code object sees them (`inject-layout` of the two contract programs
+# compiled with -DMI355X_TEST_INJECT=1)
+INJECT_ARG_STRUCTS = {"mi355x_sweep_args": SweepInjectArgs}
+DATAPATH_INJECT_ARG_STRUCTS = {"mi355x_datapath_args": DatapathInjectArgs}
+INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
+CODE_OBJECTS = ("production", "inject")
+
+
+def inject_words(req: dict) -> tuple:
+    """The six trailing argument words of a request for the inject build."""
+    inj = req.get("inject")
+    if inj is None:
+        return (INJECT_KINDS["none"], 0, 0, 0, 0, 0)
+    kind = INJECT_KINDS[inj["kind"]]
+    if req["kernel"] == "datapath" and inj["kind"] == "lds":
+        raise ValueError("the datapath kernel has no lds injection")
+    return (kind, int(inj["wg"]), int(inj.get("wave", 0)), int(inj.get("lane", 0)), int(inj["index"]),
+            int(inj["mask"]) & 0xFFFFFFFF)
+
+
+def code_object_of(req: dict) -> str:
+    which = req.get("code_object", "production")
+    if which not in CODE_OBJECTS:
+        raise ValueError(f"unknown code object {which!r}")
+    if which == "inject" and req["kernel"] not in ("sweep", "datapath"):
+        raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
+    if which != "inject" and "inject" in req:
+        raise ValueError("an injection needs \"code_object\": \"inject\"")
+    return which
+
 
 # kernel -> (symbol, lanes per workgroup)
 KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_sweep", 256),
@@ -145,6 +200,7 @@ def _filled(nbytes: int, byte: int) -> bytes:
 def plan(req: dict, base_dir: Path):
     """(buffer specs [(name, dtype, initial bytes)], args builder, workgroups) of a request."""
     k = req["kernel"]
+    code_object_of(req)                  # refuses a build or an injection the kernel does not have
     if k == "liveness":
         bufs = [("out", np.float32, _filled(32 * 32 * 4, OUT_PREFILL)), ("meta", np.uint32, _filled(16, 0)),
                 ("scratch", np.float32, _filled(16 * 64 * 4, OUT_PREFILL))]
@@ -154,6 +210,9 @@ def plan(req: dict, base_dir: Path):
         bufs = [("records", np.uint32, _filled(g * 16 * 4, 0)), ("tiles", np.float32, _filled(g * 32 * 32 * 4, OUT_PREFILL)),
                 ("arrive", np.uint32, _filled(4, 0))]
         args_grid = int(req.get("args_grid", g))
+        if code_object_of(req) == "inject":
+            return bufs, lambda p: SweepInjectArgs(p["records"], p["tiles"], p["arrive"], req["nonce"], req["iters"],
+                                                   args_grid, req["wait_ticks"], *inject_words(req)), g
         return bufs, lambda p: SweepArgs(p["records"], p["tiles"], p["arrive"], req["nonce"], req["iters"],
                                          args_grid, req["wait_ticks"]), g
     if k in ("hbm_fill", "hbm_check"):
@@ -184,11 +243,14 @@ def plan(req: dict, base_dir: Path):
         g = int(req["grid"])
         bufs = [("records", np.uint32, _filled(g * 16 * 4, OUT_PREFILL)),
                 ("tiles", np.uint32, _filled(g * 4 * 32 * 32 * 4, OUT_PREFILL))]
+        if code_object_of(req) == "inject":
+            return bufs, lambda p: DatapathInjectArgs(p["records"], p["tiles"], req["nonce"], g, *inject_words(req)), g
         return bufs, lambda p: DatapathArgs(p["records"], p["tiles"], req["nonce"], g), g
     raise ValueError(f"unknown kernel {k!r}")
 
 
-def run_request(hip: Hip, functions: dict, req: dict, base_dir: Path, outdir: Path) -> None:
+def run_request(hip: Hip, functions: dict, req: dict, base_dir: Path, outdir: Path) -> float:
+    """Runs one request; the launch-to-synchronize time in microseconds."""
     specs, make_args, wgs = plan(req, base_dir)
     symbol, lanes = KERNELS[req["kernel"]]
     bufs = [Buffer(hip, name, dtype, initial) for name, dtype, initial in specs]
@@ -196,14 +258,29 @@ def run_request(hip: Hip, functions: dict, req: dict, base_dir: Path, outdir: Pa
     size = ctypes.c_size_t(ctypes.sizeof(args))
     extra = (ctypes.c_void_p * 5)(_LAUNCH_PARAM_BUFFER_POINTER, ctypes.addressof(args), _LAUNCH_PARAM_BUFFER_SIZE,
                                   ctypes.addressof(size), _LAUNCH_PARAM_END)
+    t0 = time.perf_counter_ns()
     hip.call("hipModuleLaunchKernel", functions[symbol], wgs, 1, 1, lanes, 1, 1, 0, None, None, extra)
     hip.call("hipDeviceSynchronize")
+    launch_us = (time.perf_counter_ns() - t0) / 1e3
     for b in bufs:
         data, canary = b.read()
         np.save(outdir / f"{req['id']}.{b.name}.npy", data)
         np.save(outdir / f"{req['id']}.{b.name}.canary.npy", canary)
     for b in bufs:
         b.free()
+    return launch_us
+
+
+def load_functions(hip: Hip, path) -> dict:
+    """symbol -> function handle of every kernel of one code object."""
+    module = ctypes.c_void_p()
+    hip.call("hipModuleLoad", ctypes.byref(module), str(path).encode())
+    functions = {}
+    for symbol, _ in KERNELS.values():
+        f = ctypes.c_void_p()
+        hip.call("hipModuleGetFunction", ctypes.byref(f), module, symbol.encode())
+        functions[symbol] = f
+    return functions
 
 
 def main(argv=None) -> int:
@@ -214,23 +291,21 @@ def main(argv=None) -> int:
     req_path, outdir = Path(argv[0]).resolve(), Path(argv[1])
     requests = json.loads(req_path.read_text())
     outdir.mkdir(parents=True, exist_ok=True)
-    status = {"completed": [], "error": None, "failed": None, "hip_library": hip_library_path()}
+    status = {"completed": [], "launch_us": {}, "error": None, "failed": None, "hip_library": hip_library_path()}
     current = None
     try:
         from rocm_k8s_device_plugin_amd import _build
         hip = Hip()
         hip.call("hipInit", 0)
         hip.call("hipSetDevice", int(os.environ.get("MI355X_RAW_DEVICE", "0")))
-        module = ctypes.c_void_p()
-        hip.call("hipModuleLoad", ctypes.byref(module), str(_build.HSACO).encode())
-        functions = {}
-        for symbol, _ in KERNELS.values():
-            f = ctypes.c_void_p()
-            hip.call("hipModuleGetFunction", ctypes.byref(f), module, symbol.encode())
-            functions[symbol] = f
+        paths = {"production": _build.HSACO, "inject": _build.HSACO_INJECT}
+        loaded = {"production": load_functions(hip, paths["production"])}
         for req in requests:
             current = req["id"]
-            run_request(hip, functions, req, req_path.parent, outdir)
+            which = code_object_of(req)
+            if which not in loaded:          # the test-only build is loaded only for a request that names it
+                loaded[which] = load_functions(hip, paths[which])
+            status["launch_us"][current] = run_request(hip, loaded[which], req, req_path.parent, outdir)
             status["completed"].append(current)
         current = None
     except Exception as e:  # noqa: BLE001 - the first error ends the run, whatever it is

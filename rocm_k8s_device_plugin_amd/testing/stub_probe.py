@@ -23,6 +23,8 @@ Throughput-check replies ("perf" requests / --perf) follow the control file's
 MFMA datapath-check replies ("datapath" requests / --datapath) follow the
 "datapath" map, e.g. ``{"datapath": {"2": "stuck_bit", "5": "missing"}}``; each
 one appends "datapath:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
+Each iteration count it is asked for (a "probe" / "sweep" request line, or
+--iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 """
 import json
 import os
@@ -134,6 +136,13 @@ def _kfd_entry():
     return entry
 
 
+def _log_iters(kind, iters):
+    path = os.environ.get("MI355X_STUB_PROBE_ITERS_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"{kind} {iters}\n")
+
+
 def _parse(line):
     """One request line: (id or None, kind, timeout_s, [(ordinal, nonce, deadline_s)])."""
     parts = line.split()
@@ -144,6 +153,8 @@ def _parse(line):
     # "datapath <timeout_s> <device>..." has no iteration count
     first = {"perf": 4, "datapath": 2}.get(kind, 3)
     timeout = float(parts[1] if kind == "datapath" else parts[2])
+    if kind in ("probe", "sweep"):
+        _log_iters(kind, parts[1])
     devs = []
     for tok in parts[first:]:
         f = tok.split(":")
@@ -293,6 +304,8 @@ def main(argv):
                      else os.environ.get("ROCR_VISIBLE_DEVICES", "0")) + "\n")
     if "--serve" in argv:
         return serve()
+    if "--iters" in argv:
+        _log_iters("sweep" if "--sweep" in argv else "probe", argv[argv.index("--iters") + 1])
     nonce = 0
     for i, a in enumerate(argv):
         if a == "--nonce":
