@@ -55,6 +55,7 @@ class PyHealthEngine {
     i("perf_check_every", &c.perf_check_every);
     s("perf_action", &c.perf_action);
     i("datapath_check_every", &c.datapath_check_every);
+    i("datapath_i8_check_every", &c.datapath_i8_check_every);
     d("perf_min_hbm_read_gbps", &c.perf_min_hbm_read_gbps);
     d("perf_min_hbm_write_gbps", &c.perf_min_hbm_write_gbps);
     d("perf_min_mfma_tflops", &c.perf_min_mfma_tflops);
@@ -109,6 +110,8 @@ class PyHealthEngine {
     d["perf_checks"] = eng_->perf_checks();
     d["datapath_checks"] = eng_->datapath_checks();
     d["datapath_failures"] = eng_->datapath_failures();
+    d["datapath_i8_checks"] = eng_->datapath_i8_checks();
+    d["datapath_i8_failures"] = eng_->datapath_i8_failures();
     if (auto* p = eng_->prober()) {
       d["server_starts"] = p->server_starts.load();
       d["server_restarts"] = p->server_restarts.load();

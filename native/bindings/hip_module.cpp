@@ -47,6 +47,40 @@ py::dict to_dict(const mi355x_probe_result& r) {
 
 }  // namespace
 
+// mi355x_datapath_result or mi355x_datapath_i8_result (the same fields; stage_bad differs in length)
+template <typename R>
+py::dict datapath_dict(const R& r) {
+  py::dict d;
+  d["ordinal"] = r.ordinal;
+  d["ok"] = static_cast<bool>(r.ok);
+  d["hsa_error"] = r.hsa_error;
+  d["nonce"] = r.nonce;
+  d["grid"] = r.grid;
+  d["cu_count"] = r.cu_count;
+  d["num_xcc"] = r.num_xcc;
+  d["records_ok"] = r.records_ok;
+  d["mfma_bad"] = r.mfma_bad;
+  py::tuple stage_bad(sizeof(r.stage_bad) / sizeof(r.stage_bad[0]));
+  for (size_t i = 0; i < stage_bad.size(); ++i) stage_bad[i] = py::int_(r.stage_bad[i]);
+  d["stage_bad"] = stage_bad;
+  d["tile_bad"] = r.tile_bad;
+  d["first_bad_wg"] = r.first_bad_wg;
+  d["first_bad_stage"] = r.first_bad_stage;
+  d["first_bad_word"] = r.first_bad_word;
+  d["first_bad_got"] = r.first_bad_got;
+  d["first_bad_want"] = r.first_bad_want;
+  d["first_bad_xor"] = r.first_bad_xor;
+  d["cus_covered"] = r.cus_covered;
+  d["simds_covered"] = r.simds_covered;
+  d["xccs_covered"] = r.xccs_covered;
+  d["kernel_us"] = r.kernel_us;
+  d["total_us"] = r.total_us;
+  d["in_flight_s"] = r.in_flight_s;
+  d["kept_queue"] = static_cast<bool>(r.kept_queue);
+  d["error"] = std::string(r.error);
+  return d;
+}
+
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "gfx950 MFMA liveness probe (in-process)";
   m.def("device_count", [] {
@@ -135,33 +169,18 @@ PYBIND11_MODULE(_hip, m) {
           py::gil_scoped_release nogil;
           mi355x_hsa_datapath_check(ordinal, nonce, timeout_s, &r);
         }
-        py::dict d;
-        d["ordinal"] = r.ordinal;
-        d["ok"] = static_cast<bool>(r.ok);
-        d["hsa_error"] = r.hsa_error;
-        d["nonce"] = r.nonce;
-        d["grid"] = r.grid;
-        d["cu_count"] = r.cu_count;
-        d["num_xcc"] = r.num_xcc;
-        d["records_ok"] = r.records_ok;
-        d["mfma_bad"] = r.mfma_bad;
-        d["stage_bad"] = py::make_tuple(r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3]);
-        d["tile_bad"] = r.tile_bad;
-        d["first_bad_wg"] = r.first_bad_wg;
-        d["first_bad_stage"] = r.first_bad_stage;
-        d["first_bad_word"] = r.first_bad_word;
-        d["first_bad_got"] = r.first_bad_got;
-        d["first_bad_want"] = r.first_bad_want;
-        d["first_bad_xor"] = r.first_bad_xor;
-        d["cus_covered"] = r.cus_covered;
-        d["simds_covered"] = r.simds_covered;
-        d["xccs_covered"] = r.xccs_covered;
-        d["kernel_us"] = r.kernel_us;
-        d["total_us"] = r.total_us;
-        d["in_flight_s"] = r.in_flight_s;
-        d["kept_queue"] = static_cast<bool>(r.kept_queue);
-        d["error"] = std::string(r.error);
-        return d;
+        return datapath_dict(r);
+      },
+      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+  m.def(
+      "hsa_datapath_i8_check",
+      [](int ordinal, uint32_t nonce, double timeout_s) {
+        mi355x_datapath_i8_result r;
+        {
+          py::gil_scoped_release nogil;
+          mi355x_hsa_datapath_i8_check(ordinal, nonce, timeout_s, &r);
+        }
+        return datapath_dict(r);
       },
       py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
 }

@@ -197,6 +197,9 @@ struct Config {
   // operands, bit-exact) on idle, live GPUs; a failed verdict makes the device
   // Unhealthy until a later check passes (0 = off)
   int datapath_check_every = 0;
+  // the same cadence rule and candidates for the int8 MFMA datapath check
+  // (128-bit operands); it keeps failures of its own (0 = off)
+  int datapath_i8_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_hbm_write_gbps = 2000.0;
   double perf_min_mfma_tflops = 700.0;
@@ -255,10 +258,14 @@ class Engine {
   uint64_t crowded_skips() const { return crowded_skips_; }
   uint64_t chip_sweeps() const { return chip_sweeps_; }
   uint64_t perf_checks() const { return perf_checks_; }
-  uint64_t datapath_checks() const { return datapath_checks_; }
-  uint64_t datapath_failures() const { return datapath_failures_; }
+  uint64_t datapath_checks() const { return datapath_.checks; }
+  uint64_t datapath_failures() const { return datapath_.failures; }
   // device -> why its last MFMA datapath check failed (absent: it passed, or never ran)
   std::map<std::string, std::string> datapath_failed() const;
+  uint64_t datapath_i8_checks() const { return datapath_i8_.checks; }
+  uint64_t datapath_i8_failures() const { return datapath_i8_.failures; }
+  // the same for the int8 MFMA datapath check
+  std::map<std::string, std::string> datapath_i8_failed() const;
   // device -> (ok | degraded | failed, reason) of its last throughput check
   std::map<std::string, std::pair<std::string, std::string>> perf_verdicts() const;
   std::map<std::string, ProbeOutcome> perf_last() const;  // device -> its last throughput-check reply
@@ -306,7 +313,13 @@ class Engine {
   const GpuDevice* dev(const std::string& id) const;
   bool fabric_check();  // false: no xGMI link reading this sweep
   void perf_check(const std::map<std::string, int>& ords);
-  void datapath_check(const std::map<std::string, int>& ords);
+  struct DatapathState {
+    uint64_t checks = 0, failures = 0;
+    std::map<std::string, std::string> failed;  // guarded by mu_
+  };
+  struct DatapathKind;  // the f32 or the int8 check: request verb, wording, series names
+  static const DatapathKind kDatapathF32, kDatapathI8;
+  void datapath_check(const std::map<std::string, int>& ords, const DatapathKind& kind, DatapathState* st);
   SmiXgmiSnapshot read_xgmi();
 
   std::vector<GpuDevice> devices_;
@@ -327,8 +340,7 @@ class Engine {
   uint64_t sweeps_ = 0, identity_remaps_ = 0, crowded_skips_ = 0, chip_sweeps_ = 0, perf_checks_ = 0;
   std::map<std::string, std::pair<std::string, std::string>> perf_;  // guarded by mu_
   std::map<std::string, ProbeOutcome> perf_last_;                     // guarded by mu_
-  uint64_t datapath_checks_ = 0, datapath_failures_ = 0;
-  std::map<std::string, std::string> datapath_failed_;                // guarded by mu_
+  DatapathState datapath_, datapath_i8_;  // each check keeps failures of its own
   uint64_t xgmi_readings_ = 0;
   double last_sweep_ms_ = 0;
   int abort_fd_ = -1;

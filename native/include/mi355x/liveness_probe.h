@@ -250,6 +250,50 @@ int mi355x_hsa_datapath_check(int ordinal, uint32_t nonce, double timeout_s, mi3
 // before the verdict; stage < 0 = off.
 void mi355x_hsa_datapath_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- int8 MFMA datapath check (128-bit operands, bit-exact) -------------------
+// The same shape as the check above (one straight-line workgroup per CU, four
+// waves each, no device memory), on the wide operand form: four
+// v_mfma_i32_32x32x32_i8 stages and one v_mfma_i32_16x16x64_i8 stage per wave,
+// 4-VGPR A and B operands whose words toggle all 32 bits, int32 sums that
+// cannot overflow. Each wave checks its accumulators against a v_dot4
+// recomputation; the host checks wave 0's five tiles of every workgroup word
+// for word and names the first wrong one.
+typedef struct {
+  int ordinal;
+  int ok;                 // every record present, no device-side mismatch, every tile word exact
+  int hsa_error;
+  uint32_t nonce;
+  int grid;               // workgroups launched (= agent CU count)
+  int cu_count;
+  int num_xcc;
+  int records_ok;         // workgroups whose record is present, echoed the nonce and found no fault
+  uint32_t mfma_bad;      // MFMA elements differing from the recomputation (all waves and stages, present records)
+  uint32_t stage_bad[5];  // the same per stage
+  uint32_t tile_bad;      // wave-0 tile words differing from the host reference (present records)
+  // the first wrong tile word in (workgroup, stage, word) order; -1 / 0 when there is none
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;     // row * 32 + column (stage 4: row * 16 + column)
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor; // got ^ want: the stuck or flipped bits
+  // where the workgroups ran (reported, never required: the kernel does not wait for residency)
+  int cus_covered;        // distinct (XCC, SE, SH, CU)
+  int simds_covered;      // distinct (XCC, SE, SH, CU, SIMD) over all four waves
+  int xccs_covered;
+  double kernel_us;       // dispatch start -> end (HSA profiling)
+  double total_us;
+  double in_flight_s;     // > 0: an earlier sweep / check on this device has not completed
+  int kept_queue;         // ran on the device's kept probe queue (--serve --keep)
+  char error[160];
+} mi355x_datapath_i8_result;
+
+int mi355x_hsa_datapath_i8_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_i8_result* out);
+// Debug fault injection: flip bit `bit` of word `word` (0..1023; stage 4:
+// 0..255) of workgroup 0's stage `stage` tile of every later int8 check on
+// `ordinal` (-1 = all devices) before the verdict; stage < 0 = off.
+void mi355x_hsa_datapath_i8_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

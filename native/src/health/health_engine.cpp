@@ -467,6 +467,26 @@ void Engine::judge_liveness(const std::map<std::string, ProbeOutcome>& outcomes,
   }
 }
 
+// what tells the two MFMA datapath checks apart (Engine::datapath_check)
+struct Engine::DatapathKind {
+  const char* verb;    // the prober's request
+  const char* label;   // in reasons and log lines
+  const char* span;
+  const char* checks_total;
+  const char* checks_help;
+  const char* failures_total;
+  const char* failures_help;
+};
+
+const Engine::DatapathKind Engine::kDatapathF32 = {
+    "datapath", "datapath check", "health.datapath_check", "mi355x_dp_datapath_checks_total",
+    "MFMA datapath checks run (full-width operands, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_check_failures_total", "MFMA datapath checks that did not pass"};
+const Engine::DatapathKind Engine::kDatapathI8 = {
+    "datapath_i8", "datapath i8 check", "health.datapath_i8_check", "mi355x_dp_datapath_i8_checks_total",
+    "int8 MFMA datapath checks run (128-bit operands, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_i8_check_failures_total", "int8 MFMA datapath checks that did not pass"};
+
 void Engine::liveness_pass(Reasons* reasons) {
   std::map<std::string, int> ords = judged_ordinals(*reasons);
   std::set<std::string> busy;
@@ -502,15 +522,20 @@ void Engine::liveness_pass(Reasons* reasons) {
     if (!cand.empty()) perf_check(cand);
   }
   // the same idle GPUs, under the same rule: `idle` is empty while busy state is unknown
-  if (cfg_.datapath_check_every > 0 && sweeps_ % static_cast<uint64_t>(cfg_.datapath_check_every) == 0) {
+  const std::pair<int, std::pair<const DatapathKind*, DatapathState*>> datapath_checks[] = {
+      {cfg_.datapath_check_every, {&kDatapathF32, &datapath_}},
+      {cfg_.datapath_i8_check_every, {&kDatapathI8, &datapath_i8_}}};
+  for (const auto& [every, check] : datapath_checks) {
+    if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
     for (const auto& [id, o] : probe_ords)
       if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = o;
-    if (!cand.empty()) datapath_check(cand);
+    if (!cand.empty()) datapath_check(cand, *check.first, check.second);
   }
   std::lock_guard<std::mutex> lk(mu_);
-  for (const auto& [id, why] : datapath_failed_)
-    if (reasons->count(id)) (*reasons)[id].push_back(why);
+  for (const DatapathState* st : {&datapath_, &datapath_i8_})
+    for (const auto& [id, why] : st->failed)
+      if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
     if (reasons->count(id) && (pv.first == "failed" || (pv.first == "degraded" && cfg_.perf_action == "unhealthy")))
       (*reasons)[id].push_back(pv.second);
@@ -930,47 +955,52 @@ void Engine::perf_check(const std::map<std::string, int>& ords) {
   }
 }
 
-// The MFMA datapath check on idle GPUs: a reply that is not ok (the verdict
+// The MFMA datapath checks on idle GPUs: a reply that is not ok (the verdict
 // names stage, word and xor of the first wrong word) makes the device
-// Unhealthy until a later check passes.
-void Engine::datapath_check(const std::map<std::string, int>& ords) {
-  trace::Span span("health.datapath_check", "health", {{"devices", std::to_string(ords.size())}});
+// Unhealthy until a later check of the same kind passes. Each kind keeps
+// failures of its own: a passing f32 check never clears an int8 failure, nor
+// the reverse.
+void Engine::datapath_check(const std::map<std::string, int>& ords, const DatapathKind& kind, DatapathState* st) {
+  trace::Span span(kind.span, "health", {{"devices", std::to_string(ords.size())}});
   std::vector<int> uniq;
   for (const auto& [id, o] : ords) uniq.push_back(o);
-  const auto by_ord = prober_->probe(uniq, {}, "datapath");
-  datapath_checks_++;
+  const auto by_ord = prober_->probe(uniq, {}, kind.verb);
+  st->checks++;
   auto& m = metrics::global();
-  m.inc("mi355x_dp_datapath_checks_total", {}, 1.0,
-        "MFMA datapath checks run (full-width operands, bit-exact, on the idle GPUs)");
+  m.inc(kind.checks_total, {}, 1.0, kind.checks_help);
   for (const auto& [id, ord] : ords) {
     auto it = by_ord.find(ord);
     if (it == by_ord.end()) continue;
     const ProbeOutcome& o = it->second;
     if (o.interrupted) continue;  // stopped by the shutdown, not failed: the last result stands
-    const std::string why = o.ok ? std::string() : "datapath check: " + o.reason;
+    const std::string why = o.ok ? std::string() : std::string(kind.label) + ": " + o.reason;
     bool was_failed;
     {
       std::lock_guard<std::mutex> lk(mu_);
-      was_failed = datapath_failed_.count(id) > 0;
+      was_failed = st->failed.count(id) > 0;
       if (o.ok)
-        datapath_failed_.erase(id);
+        st->failed.erase(id);
       else
-        datapath_failed_[id] = why;
+        st->failed[id] = why;
     }
     if (!o.ok) {
-      datapath_failures_++;
-      m.inc("mi355x_dp_datapath_check_failures_total", {{"device", id}}, 1.0,
-            "MFMA datapath checks that did not pass");
+      st->failures++;
+      m.inc(kind.failures_total, {{"device", id}}, 1.0, kind.failures_help);
     }
     if (was_failed != !o.ok)
-      glog::log(o.ok ? glog::kInfo : glog::kWarning, __FILE__, __LINE__, "device %s: datapath check %s %s", id.c_str(),
+      glog::log(o.ok ? glog::kInfo : glog::kWarning, __FILE__, __LINE__, "device %s: %s %s %s", id.c_str(), kind.label,
                 o.ok ? "passes again" : "failed:", why.c_str());
   }
 }
 
 std::map<std::string, std::string> Engine::datapath_failed() const {
   std::lock_guard<std::mutex> lk(mu_);
-  return datapath_failed_;
+  return datapath_.failed;
+}
+
+std::map<std::string, std::string> Engine::datapath_i8_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_i8_.failed;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

@@ -3,3 +3,4 @@
 // the kernels of all source files are compiled as one translation unit.
 #include "liveness_kernel.hip"
 #include "datapath_kernel.hip"
+#include "datapath_i8_kernel.hip"

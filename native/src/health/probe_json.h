@@ -1,5 +1,5 @@
-// The JSON objects the probe prints for a chip sweep, a throughput check and a
-// datapath check (shared by probe_main.cpp and the contract CLIs under
+// The JSON objects the probe prints for a chip sweep, a throughput check and the
+// two datapath checks (shared by probe_main.cpp and the contract CLIs under
 // native/tests, so a test sees exactly the line the prober parses), and the
 // blank result each of them starts from. Strings grow as needed: a long
 // escaped `error` next to wide numbers is never cut.
@@ -46,7 +46,7 @@ __attribute__((format(printf, 1, 2))) inline std::string json_format(const char*
 }
 
 // The result of a check on `ordinal` before anything is known: all zero but
-// what the type defines otherwise -- the datapath result's first_bad_* = -1
+// what the type defines otherwise -- the datapath results' first_bad_* = -1
 // ("none"). hbm_first_bad of the throughput result stays 0 here: a reply that
 // never reached the runtime carries 0, mi355x_hsa_perf_check sets its own -1.
 template <typename R>
@@ -54,7 +54,7 @@ R blank_result(int ordinal, uint32_t nonce) {
   R r{};
   r.ordinal = ordinal;
   r.nonce = nonce;
-  if constexpr (std::is_same_v<R, mi355x_datapath_result>)
+  if constexpr (std::is_same_v<R, mi355x_datapath_result> || std::is_same_v<R, mi355x_datapath_i8_result>)
     r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
   return r;
 }
@@ -111,6 +111,20 @@ inline std::string datapath_json(const mi355x_datapath_result& r) {
       r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered,
       r.simds_covered, r.xccs_covered, r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false",
       json_escape(r.error).c_str());
+}
+
+inline std::string datapath_i8_json(const mi355x_datapath_i8_result& r) {
+  return json_format(
+      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
+      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u],\"tile_bad\":%u,"
+      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
+      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
+      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"error\":\"%s\"}",
+      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
+      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.tile_bad,
+      r.first_bad_wg, r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor,
+      r.cus_covered, r.simds_covered, r.xccs_covered, r.kernel_us, r.total_us, r.in_flight_s,
+      r.kept_queue ? "true" : "false", json_escape(r.error).c_str());
 }
 
 }  // namespace mi355x

@@ -6,10 +6,12 @@
 //   mi355x-liveness-probe --sweep [--devices ..]   (every CU of every XCD, see mi355x_chip_sweep)
 //   mi355x-liveness-probe --perf [--perf-mib M]     (HBM bandwidth + pattern, sustained MFMA rate, clocks)
 //   mi355x-liveness-probe --datapath [--devices ..] (full-width bit-exact MFMA operands, see mi355x_mfma_datapath)
+//   mi355x-liveness-probe --datapath-i8 [--devices ..] (128-bit int8 operands, see mi355x_mfma_datapath_i8)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
 //   --corrupt-datapath S:W:B[@O]: flip bit B of word W of workgroup 0's stage S tile before the datapath verdict
+//   --corrupt-datapath-i8 S:W:B[@O]: the same for the int8 datapath check (S 0..4)
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -72,6 +74,7 @@ uint64_t mono_ns() {
 }
 
 using mi355x::blank_result;
+using mi355x::datapath_i8_json;
 using mi355x::datapath_json;
 using mi355x::json_escape;
 using mi355x::perf_json;
@@ -127,6 +130,12 @@ int datapath_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_resu
 void datapath_corrupt(int stage, int word, int bit, int ordinal) {
   mi355x_hsa_datapath_corrupt(stage, word, bit, ordinal);
 }
+int datapath_i8_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_i8_result* r) {
+  return mi355x_hsa_datapath_i8_check(o, nonce, timeout_s, r);
+}
+void datapath_i8_corrupt(int stage, int word, int bit, int ordinal) {
+  mi355x_hsa_datapath_i8_corrupt(stage, word, bit, ordinal);
+}
 void init_phases(double out[5]) { mi355x_hsa_init_phases(out); }
 void defer_teardown() { mi355x_hsa_probe_defer_release(1); }
 void teardown() { mi355x_hsa_probe_release(); }
@@ -163,6 +172,10 @@ void perf_poison(uint64_t) {}
 void datapath_corrupt(int, int, int, int) {}
 int datapath_check(int o, uint32_t nonce, double, mi355x_datapath_result* r) {
   return needs_hsa_build("--datapath", blank_result<mi355x_datapath_result>(o, nonce), r);
+}
+void datapath_i8_corrupt(int, int, int, int) {}
+int datapath_i8_check(int o, uint32_t nonce, double, mi355x_datapath_i8_result* r) {
+  return needs_hsa_build("--datapath-i8", blank_result<mi355x_datapath_i8_result>(o, nonce), r);
 }
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
   auto blank = blank_result<mi355x_perf_result>(o, nonce);
@@ -318,7 +331,7 @@ bool run_on_each(const std::vector<int>& ords, const std::vector<uint32_t>& nonc
   return ok;
 }
 
-// --sweep / --perf / --datapath and the server's requests of those kinds.
+// --sweep / --perf / --datapath / --datapath-i8 and the server's requests of those kinds.
 // `iters`: the sweep's tile iterations or the throughput check's MFMA
 // iterations; `bytes`: the throughput check's HBM buffer.
 bool run_check(const std::string& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
@@ -331,12 +344,16 @@ bool run_check(const std::string& kind, const std::vector<int>& ords, const std:
     return run_on_each(ords, nonces, timeouts, n, [=](int o, uint32_t nonce, double t, mi355x_perf_result* r) {
       return perf_check(o, nonce, bytes, iters, t, r);
     }, perf_json, json);
+  if (kind == "datapath_i8")
+    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_i8_result* r) {
+      return datapath_i8_check(o, nonce, t, r);
+    }, datapath_i8_json, json);
   return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_result* r) {
     return datapath_check(o, nonce, t, r);
   }, datapath_json, json);
 }
 
-// "S:W:B" or "S:W:B@O" of --corrupt-datapath
+// "S:W:B" or "S:W:B@O" of --corrupt-datapath and --corrupt-datapath-i8
 bool parse_corrupt_datapath(const char* spec, int out[4]) {
   out[3] = -1;
   char tail = 0;
@@ -359,6 +376,7 @@ std::string devices_json(const std::vector<mi355x_probe_result>& results) {
 //     [@<id> ]sweep <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]perf <mfma_iters> <timeout_s> <mib> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // is answered with one JSON line {"id":..,"ok":..,"t_ready_ns":..,"devices":[..]}
 // ("id" only for a tagged request). A device's own deadline replaces the
 // request's timeout for that device: the plugin gives GPUs that run other
@@ -386,7 +404,7 @@ constexpr int kMaxServeWorkers = 64;  // beyond this a tagged request is answere
 struct ServeRequest {
   bool tagged = false;
   unsigned long long id = 0;
-  std::string kind;  // probe | sweep | perf | datapath
+  std::string kind;  // probe | sweep | perf | datapath | datapath_i8
   int iters = 0;
   double timeout_s = 0;
   unsigned long long perf_mib = 0;
@@ -409,6 +427,9 @@ bool parse_request(const std::string& line, ServeRequest* r) {
   if (std::strncmp(p, "perf ", 5) == 0) {
     r->kind = "perf";
     parsed = std::sscanf(p, "perf %d %lf %llu %n", &r->iters, &r->timeout_s, &r->perf_mib, &consumed) >= 3;
+  } else if (std::strncmp(p, "datapath_i8 ", 12) == 0) {
+    r->kind = "datapath_i8";
+    parsed = std::sscanf(p, "datapath_i8 %lf %n", &r->timeout_s, &consumed) >= 1;
   } else if (std::strncmp(p, "datapath ", 9) == 0) {
     r->kind = "datapath";
     parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;
@@ -474,8 +495,9 @@ void answer(const ServeRequest& r, int n) {
   std::snprintf(head, sizeof(head), "{%s\"ok\":%s,\"hip_device_count\":%d,\"sweep\":%s,\"perf\":%s,\"t_ready_ns\":%llu,",
                 id_field(r).c_str(), ok ? "true" : "false", n, r.kind == "sweep" ? "true" : "false",
                 r.kind == "perf" ? "true" : "false", static_cast<unsigned long long>(mono_ns()));
-  // only a datapath reply carries the key: the other replies stay as they were
-  emit_line(std::string(head) + (r.kind == "datapath" ? "\"datapath\":true," : "") + "\"devices\":" + body + "}");
+  // only a datapath reply carries its key: the other replies stay as they were
+  const char* key = r.kind == "datapath" ? "\"datapath\":true," : r.kind == "datapath_i8" ? "\"datapath_i8\":true," : "";
+  emit_line(std::string(head) + key + "\"devices\":" + body + "}");
   teardown();  // queues/executables go, the runtime (and the kfd process) stays
 }
 
@@ -589,6 +611,7 @@ int main(int argc, char** argv) {
   bool sweep_mode = false;
   bool perf_mode = false;
   bool datapath_mode = false;
+  bool datapath_i8_mode = false;
   uint64_t perf_mib = 4096;
   int perf_iters = 1 << 16;
   uint64_t peer_bytes = 64ull << 20;
@@ -639,6 +662,15 @@ int main(int argc, char** argv) {
         return 2;
       }
       datapath_corrupt(c[0], c[1], c[2], c[3]);
+    } else if (a == "--datapath-i8") {
+      datapath_i8_mode = true;
+    } else if (a == "--corrupt-datapath-i8") {
+      int c[4];
+      if (!parse_corrupt_datapath(next("--corrupt-datapath-i8"), c)) {
+        std::fprintf(stderr, "--corrupt-datapath-i8 must be STAGE:WORD:BIT[@ORDINAL]\n");
+        return 2;
+      }
+      datapath_i8_corrupt(c[0], c[1], c[2], c[3]);
     } else if (a == "--perf-mib") {
       perf_mib = std::strtoull(next("--perf-mib"), nullptr, 0);
     } else if (a == "--perf-iters") {
@@ -662,6 +694,7 @@ int main(int argc, char** argv) {
       std::printf("usage: %s [--devices all|0,1,..] [--nonce N] [--iters N] [--identify] [--timeout S] "
                   "[--sample-init PERIOD_US] [--exit shutdown|release|fast] [--serve [--keep]] [--peer [--peer-bytes B] [--peer-reps R]] [--sweep] "
                   "[--perf [--perf-mib M] [--perf-iters N] [--poison-hbm UNIT]] [--datapath [--corrupt-datapath S:W:B[@ORDINAL]]] "
+                  "[--datapath-i8 [--corrupt-datapath-i8 S:W:B[@ORDINAL]]] "
                   "[--corrupt-word K[@ORDINAL]] [--hip-stream own|null]\n",
                   argv[0]);
       return 0;
@@ -712,8 +745,8 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> nonces;
   for (size_t i = 0; i < ords.size(); ++i) nonces.push_back(nonce + static_cast<uint32_t>(i));
   const std::vector<double> timeouts(ords.size(), timeout_s);
-  if (perf_mode || datapath_mode || sweep_mode) {
-    const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : "sweep";
+  if (perf_mode || datapath_mode || datapath_i8_mode || sweep_mode) {
+    const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : datapath_i8_mode ? "datapath_i8" : "sweep";
     std::string body;
     const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
     std::printf("{\"ok\":%s,\"%s\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"

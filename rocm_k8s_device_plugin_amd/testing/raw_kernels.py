@@ -13,15 +13,16 @@ REQUESTS.json is a list of requests, run in order:
     {"id": ..., "kernel": "hbm_check", "n16": u, "grid": g, "threads": t, "seed": s, "buf_npy": file}
     {"id": ..., "kernel": "burn", "nonce": n, "iters": k, "grid": g, "hbm_counters": [4 words]}
     {"id": ..., "kernel": "datapath", "nonce": n, "grid": g}
+    {"id": ..., "kernel": "datapath_i8", "nonce": n, "grid": g}
 
-A sweep or datapath request may add "code_object": "inject": the kernel then comes from
+A sweep, datapath or datapath_i8 request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
-the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h), and may add
+the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h), and may add
 
     "inject": {"kind": "mfma" | "lds", "wg": w, "wave": v, "lane": l, "index": i, "mask": m}
 
 (one data word xor-ed with m: accumulator register i of that lane after the last MFMA -- for the
-datapath i = stage * 16 + register -- or LDS pattern word i; wave and lane are unused for "lds").
+datapath kernels i = stage * 16 + register -- or LDS pattern word i; wave and lane are unused for "lds").
 Without "inject" the hook is off. Every other request uses the production code object.
 
 For each request OUTDIR gets <id>.<buffer>.npy and <id>.<buffer>.canary.npy
@@ -100,6 +101,20 @@ class DatapathInjectArgs(ctypes.Structure):
 # compiled with -DMI355X_TEST_INJECT=1)
 INJECT_ARG_STRUCTS = {"mi355x_sweep_args": SweepInjectArgs}
 DATAPATH_INJECT_ARG_STRUCTS = {"mi355x_datapath_args": DatapathInjectArgs}
+
+
+class DatapathI8Args(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("nonce", _u32), ("grid", _u32)]
+
+
+class DatapathI8InjectArgs(ctypes.Structure):
+    _fields_ = DatapathI8Args._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_i8_kernel.h (native/tests/datapath_i8_contract_cli.cpp prints that header's layouts)
+DATAPATH_I8_ARG_STRUCTS = {"mi355x_datapath_i8_args": DatapathI8Args}
+DATAPATH_I8_INJECT_ARG_STRUCTS = {"mi355x_datapath_i8_args": DatapathI8InjectArgs}
+DATAPATH_I8_WG_WORDS = 4 * 32 * 32 + 16 * 16         # wave 0's five tiles of one workgroup
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -110,8 +125,8 @@ def inject_words(req: dict) -> tuple:
     if inj is None:
         return (INJECT_KINDS["none"], 0, 0, 0, 0, 0)
     kind = INJECT_KINDS[inj["kind"]]
-    if req["kernel"] == "datapath" and inj["kind"] == "lds":
-        raise ValueError("the datapath kernel has no lds injection")
+    if req["kernel"] in ("datapath", "datapath_i8") and inj["kind"] == "lds":
+        raise ValueError("the datapath kernels have no lds injection")
     return (kind, int(inj["wg"]), int(inj.get("wave", 0)), int(inj.get("lane", 0)), int(inj["index"]),
             int(inj["mask"]) & 0xFFFFFFFF)
 
@@ -120,7 +135,7 @@ def code_object_of(req: dict) -> str:
     which = req.get("code_object", "production")
     if which not in CODE_OBJECTS:
         raise ValueError(f"unknown code object {which!r}")
-    if which == "inject" and req["kernel"] not in ("sweep", "datapath"):
+    if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -130,7 +145,8 @@ def code_object_of(req: dict) -> str:
 # kernel -> (symbol, lanes per workgroup)
 KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_sweep", 256),
            "hbm_fill": ("mi355x_hbm_fill", 256), "hbm_check": ("mi355x_hbm_check", 256),
-           "burn": ("mi355x_mfma_burn", 256), "datapath": ("mi355x_mfma_datapath", 256)}
+           "burn": ("mi355x_mfma_burn", 256), "datapath": ("mi355x_mfma_datapath", 256),
+           "datapath_i8": ("mi355x_mfma_datapath_i8", 256)}
 
 _H2D, _D2H = 1, 2
 _LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
@@ -246,6 +262,14 @@ def plan(req: dict, base_dir: Path):
         if code_object_of(req) == "inject":
             return bufs, lambda p: DatapathInjectArgs(p["records"], p["tiles"], req["nonce"], g, *inject_words(req)), g
         return bufs, lambda p: DatapathArgs(p["records"], p["tiles"], req["nonce"], g), g
+    if k == "datapath_i8":
+        g = int(req["grid"])
+        bufs = [("records", np.uint32, _filled(g * 16 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * DATAPATH_I8_WG_WORDS * 4, OUT_PREFILL))]
+        if code_object_of(req) == "inject":
+            return bufs, lambda p: DatapathI8InjectArgs(p["records"], p["tiles"], req["nonce"], g,
+                                                        *inject_words(req)), g
+        return bufs, lambda p: DatapathI8Args(p["records"], p["tiles"], req["nonce"], g), g
     raise ValueError(f"unknown kernel {k!r}")
 
 

@@ -23,6 +23,9 @@ Throughput-check replies ("perf" requests / --perf) follow the control file's
 MFMA datapath-check replies ("datapath" requests / --datapath) follow the
 "datapath" map, e.g. ``{"datapath": {"2": "stuck_bit", "5": "missing"}}``; each
 one appends "datapath:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
+int8 MFMA datapath-check replies ("datapath_i8" requests / --datapath-i8)
+follow the "datapath_i8" map with the same modes; each one appends
+"datapath_i8:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 """
@@ -110,6 +113,34 @@ def _datapath_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return d
 
 
+def _datapath_i8_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """int8 MFMA datapath-check reply (kind "datapath_i8"); the modes of
+    _datapath_device, from the control file's "datapath_i8" map (stuck_bit: bit
+    30 of every stage-4 word of one CU's tile)."""
+    log = os.environ.get("MI355X_STUB_PROBE_LOG")
+    if log:
+        with open(log, "a") as f:
+            f.write(f"datapath_i8:{ordinal_reported if host_ordinal is None else host_ordinal}\n")
+    d = {**_identity(ordinal_reported if host_ordinal is None else host_ordinal),
+         "ordinal": ordinal_reported, "ok": mode == "ok", "hsa_error": 0, "nonce": nonce, "grid": 256, "cu_count": 256,
+         "num_xcc": 8, "records_ok": 256, "mfma_bad": 0, "stage_bad": [0, 0, 0, 0, 0], "tile_bad": 0,
+         "first_bad_wg": -1, "first_bad_stage": -1, "first_bad_word": -1, "first_bad_got": 0, "first_bad_want": 0,
+         "first_bad_xor": 0, "cus_covered": 256, "simds_covered": 1024, "xccs_covered": 8, "kernel_us": 25.0,
+         "total_us": 2000.0, "in_flight_s": 0.0, "kept_queue": True, "error": ""}
+    if mode == "stuck_bit":
+        d.update(records_ok=255, tile_bad=131, first_bad_wg=17, first_bad_stage=4, first_bad_word=5,
+                 first_bad_got=0x0A123456, first_bad_want=0x4A123456, first_bad_xor=0x40000000,
+                 error="255/256 workgroups exact (device_bad=0 tile_bad=131); first bad: wg 17 stage 4 word 5 "
+                       "xor 0x40000000 (bit 30)")
+    elif mode == "missing":
+        d.update(records_ok=254, cus_covered=254, simds_covered=1016,
+                 error="254/256 workgroups exact (device_bad=0 tile_bad=0)")
+    elif mode == "device_bad":
+        d.update(records_ok=255, mfma_bad=12, stage_bad=[0, 0, 0, 0, 12],
+                 error="255/256 workgroups exact (device_bad=12 tile_bad=0)")
+    return d
+
+
 def _kfd_entry():
     """Like a kept-queue server: a kfd proc entry with one queue per GPU id
     (MI355X_STUB_KFD_PROC / MI355X_STUB_KFD_GPUIDS), removed on exit.
@@ -150,9 +181,9 @@ def _parse(line):
     if parts and parts[0].startswith("@"):
         rid, parts = int(parts[0][1:]), parts[1:]
     kind = parts[0]
-    # "datapath <timeout_s> <device>..." has no iteration count
-    first = {"perf": 4, "datapath": 2}.get(kind, 3)
-    timeout = float(parts[1] if kind == "datapath" else parts[2])
+    # "datapath <timeout_s> <device>..." and "datapath_i8 ..." have no iteration count
+    first = {"perf": 4, "datapath": 2, "datapath_i8": 2}.get(kind, 3)
+    timeout = float(parts[1] if kind in ("datapath", "datapath_i8") else parts[2])
     if kind in ("probe", "sweep"):
         _log_iters(kind, parts[1])
     devs = []
@@ -198,6 +229,11 @@ def serve():
             if dmode == "hang":
                 time.sleep(3600)
             return _datapath_device(int(o), dmode, n, host_ordinal=int(hosto))
+        if kind == "datapath_i8":
+            dmode = ctl.get("datapath_i8", {}).get(hosto, "ok")
+            if dmode == "hang":
+                time.sleep(3600)
+            return _datapath_i8_device(int(o), dmode, n, host_ordinal=int(hosto))
         mode = ctl.get(hosto, "ok")
         if mode == "server_fail":
             mode = "fail"
@@ -276,8 +312,8 @@ def serve():
             th.join()
         doc = {"ok": all(d["ok"] for d in res), "hip_device_count": 8, "sweep": kind == "sweep",
                "t_ready_ns": time.monotonic_ns(), "devices": res}
-        if kind == "datapath":
-            doc["datapath"] = True
+        if kind in ("datapath", "datapath_i8"):
+            doc[kind] = True
         if rid is not None:
             doc = {"id": rid, **doc}
         with out_mu:
@@ -318,6 +354,11 @@ def main(argv):
     if "--datapath" in argv:
         d = _datapath_device(0, _control().get("datapath", {}).get(ordinal, "ok"), nonce, host_ordinal=int(ordinal))
         print(json.dumps({"ok": d["ok"], "datapath": True, "hip_device_count": 1, "devices": [d]}))
+        return 0 if d["ok"] else 1
+    if "--datapath-i8" in argv:
+        d = _datapath_i8_device(0, _control().get("datapath_i8", {}).get(ordinal, "ok"), nonce,
+                                host_ordinal=int(ordinal))
+        print(json.dumps({"ok": d["ok"], "datapath_i8": True, "hip_device_count": 1, "devices": [d]}))
         return 0 if d["ok"] else 1
     ctl = _control()
     mode = ctl.get(ordinal, "ok")
