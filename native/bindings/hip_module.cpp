@@ -77,6 +77,8 @@ py::dict datapath_dict(const R& r) {
   d["total_us"] = r.total_us;
   d["in_flight_s"] = r.in_flight_s;
   d["kept_queue"] = static_cast<bool>(r.kept_queue);
+  d["kfd_node_id"] = r.kfd_node_id;
+  d["pci_bus_id"] = std::string(r.pci_bus_id);
   d["error"] = std::string(r.error);
   return d;
 }

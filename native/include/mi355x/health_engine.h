@@ -310,6 +310,7 @@ class Engine {
   std::map<std::string, ProbeOutcome> verify_identity(const std::map<std::string, int>& ords,
                                                       const std::map<std::string, ProbeOutcome>& outcomes);
   bool identity_matches(const GpuDevice& d, const ProbeOutcome& o) const;
+  bool check_reply_is_from(const std::string& id, const ProbeOutcome& o, const char* what);
   const GpuDevice* dev(const std::string& id) const;
   bool fabric_check();  // false: no xGMI link reading this sweep
   void perf_check(const std::map<std::string, int>& ords);

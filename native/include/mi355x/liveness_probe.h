@@ -152,6 +152,9 @@ typedef struct {
   // outstanding sweep per device, so a wedged GPU leaks one queue, not one per cadence)
   double in_flight_s;
   int kept_queue;         // ran on the device's kept probe queue (--serve --keep), no queue of its own
+  // the agent the check ran on, as in mi355x_probe_result: -1 and "" when the check never reached a device
+  int kfd_node_id;
+  char pci_bus_id[32];    // dddd:bb:dd.f
   char error[160];
 } mi355x_sweep_result;
 
@@ -197,6 +200,9 @@ typedef struct {
   double total_us;
   double in_flight_s;        // > 0: an earlier sweep / check on this device has not completed
   int kept_queue;            // ran on the device's kept probe queue (--serve --keep)
+  // the agent the check ran on, as in mi355x_probe_result: -1 and "" when the check never reached a device
+  int kfd_node_id;
+  char pci_bus_id[32];    // dddd:bb:dd.f
   char error[160];
 } mi355x_perf_result;
 
@@ -241,6 +247,9 @@ typedef struct {
   double total_us;
   double in_flight_s;     // > 0: an earlier sweep / check on this device has not completed
   int kept_queue;         // ran on the device's kept probe queue (--serve --keep)
+  // the agent the check ran on, as in mi355x_probe_result: -1 and "" when the check never reached a device
+  int kfd_node_id;
+  char pci_bus_id[32];    // dddd:bb:dd.f
   char error[160];
 } mi355x_datapath_result;
 
@@ -285,6 +294,9 @@ typedef struct {
   double total_us;
   double in_flight_s;     // > 0: an earlier sweep / check on this device has not completed
   int kept_queue;         // ran on the device's kept probe queue (--serve --keep)
+  // the agent the check ran on, as in mi355x_probe_result: -1 and "" when the check never reached a device
+  int kfd_node_id;
+  char pci_bus_id[32];    // dddd:bb:dd.f
   char error[160];
 } mi355x_datapath_i8_result;
 

@@ -228,6 +228,15 @@ bool Engine::kfd_load(const std::set<std::string>& exclude, std::map<int64_t, st
   return true;
 }
 
+namespace {
+// whether a reply carries its agent's PCI location or kfd node id
+bool names_agent(const ProbeOutcome& o) {
+  unsigned D = 0, B = 0, Dv = 0, F = 0;
+  return o.kfd_node_id >= 0 ||
+         (!o.pci_bus_id.empty() && std::sscanf(o.pci_bus_id.c_str(), "%x:%x:%x.%x", &D, &B, &Dv, &F) == 4);
+}
+}  // namespace
+
 bool Engine::identity_matches(const GpuDevice& d, const ProbeOutcome& o) const {
   int dom = -1, loc = -1;
   unsigned D = 0, B = 0, Dv = 0, F = 0;
@@ -261,6 +270,7 @@ std::map<std::string, ProbeOutcome> Engine::verify_identity(const std::map<std::
   }
   std::map<std::string, ProbeOutcome> fixed;
   std::map<std::string, int> new_ords;
+  std::set<int> taken;  // ordinals a reply's identity gave to a device
   for (const auto& [id, ord] : ords) {
     const GpuDevice* d = dev(id);
     if (!d) continue;
@@ -271,11 +281,22 @@ std::map<std::string, ProbeOutcome> Engine::verify_identity(const std::map<std::
       if (auto it = by_node.find(d->node_id); it != by_node.end()) hit = &it->second;
     if (hit && identity_matches(*d, *hit->second)) {
       new_ords[id] = hit->first;
+      taken.insert(hit->first);
       fixed[id] = *hit->second;
       if (hit->first != ord)
         MI_LOG(kError, "probe identity: device %s is ordinal %d, not %d (verdict re-keyed)", id.c_str(), hit->first,
                ord);
     }
+  }
+  // a reply that names no agent (it never reached a device, or comes from a
+  // probe that prints no identity) says nothing against its ordinal: the device
+  // keeps it, unless a reply that does name its agent showed whose it is
+  for (const auto& [id, ord] : ords) {
+    if (new_ords.count(id) || taken.count(ord)) continue;
+    auto it = outcomes.find(id);
+    if (it == outcomes.end() || names_agent(it->second)) continue;
+    new_ords[id] = ord;
+    fixed[id] = it->second;
   }
   std::string lost;
   for (const auto& [id, ord] : ords)
@@ -518,7 +539,7 @@ void Engine::liveness_pass(Reasons* reasons) {
   if (cfg_.perf_check_every > 0 && sweeps_ % static_cast<uint64_t>(cfg_.perf_check_every) == 0) {
     std::map<std::string, int> cand;
     for (const auto& [id, o] : probe_ords)
-      if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = o;
+      if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = ords.at(id);  // as remapped by this pulse
     if (!cand.empty()) perf_check(cand);
   }
   // the same idle GPUs, under the same rule: `idle` is empty while busy state is unknown
@@ -529,7 +550,7 @@ void Engine::liveness_pass(Reasons* reasons) {
     if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
     for (const auto& [id, o] : probe_ords)
-      if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = o;
+      if (idle.count(id) && track_[id].live && ords.count(id)) cand[id] = ords.at(id);
     if (!cand.empty()) datapath_check(cand, *check.first, check.second);
   }
   std::lock_guard<std::mutex> lk(mu_);
@@ -898,6 +919,19 @@ std::vector<std::string> Engine::perf_problems(const ProbeOutcome& o) const {
   return out;
 }
 
+// A check's verdict persists, so it is taken only from a reply of the device's
+// own agent: with a stale ordinal map another agent answers, and that reply is
+// no verdict on this device (the next sweep's probes re-key the map).
+bool Engine::check_reply_is_from(const std::string& id, const ProbeOutcome& o, const char* what) {
+  const GpuDevice* d = dev(id);
+  if (!d || identity_matches(*d, o)) return true;
+  MI_LOG(kError, "%s: reply from agent %s (kfd node %d), not device %s: no verdict this sweep", what,
+         o.pci_bus_id.c_str(), o.kfd_node_id, id.c_str());
+  metrics::global().inc("mi355x_dp_check_identity_mismatch_total", {{"device", id}}, 1.0,
+                        "check replies dropped because another agent than the device's answered");
+  return false;
+}
+
 void Engine::perf_check(const std::map<std::string, int>& ords) {
   trace::Span span("health.perf_check", "health", {{"devices", std::to_string(ords.size())}});
   std::vector<int> uniq;
@@ -912,6 +946,7 @@ void Engine::perf_check(const std::map<std::string, int>& ords) {
     if (it == by_ord.end()) continue;
     const ProbeOutcome& o = it->second;
     if (o.interrupted) continue;  // stopped by the shutdown, not failed: the last result stands
+    if (!check_reply_is_from(id, o, "throughput check")) continue;
     std::string state = "ok", why;
     if (!o.ok) {
       state = "failed";
@@ -973,6 +1008,7 @@ void Engine::datapath_check(const std::map<std::string, int>& ords, const Datapa
     if (it == by_ord.end()) continue;
     const ProbeOutcome& o = it->second;
     if (o.interrupted) continue;  // stopped by the shutdown, not failed: the last result stands
+    if (!check_reply_is_from(id, o, kind.label)) continue;
     const std::string why = o.ok ? std::string() : std::string(kind.label) + ": " + o.reason;
     bool was_failed;
     {

@@ -322,6 +322,8 @@ struct Check {
       return false;
     }
     if (const double s = in_flight_for(ordinal); s > 0) {
+      ag = &g_rt.gpus[ordinal];
+      identify();
       out->in_flight_s = s;
       out->hsa_error = -1;
       std::snprintf(out->error, sizeof(out->error),
@@ -329,6 +331,7 @@ struct Check {
       return finish(), false;
     }
     ag = &g_rt.gpus[ordinal];
+    identify();
     uint32_t cus = 0, xcc = 0;
     H().hsa_agent_get_info(ag->agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT), &cus);
     H().hsa_agent_get_info(ag->agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_NUM_XCC), &xcc);
@@ -358,6 +361,15 @@ struct Check {
       return finish(), false;
     }
     return true;
+  }
+
+  // which agent the reply speaks of, as a probe's reply names it (hsa_probe.cpp fill_identity)
+  void identify() {
+    uint32_t node = 0;
+    if (H().hsa_agent_get_info(ag->agent, static_cast<hsa_agent_info_t>(HSA_AMD_AGENT_INFO_DRIVER_NODE_ID), &node) ==
+        HSA_STATUS_SUCCESS)
+      out->kfd_node_id = static_cast<int>(node);
+    bus_id(*ag, out->pci_bus_id, sizeof(out->pci_bus_id));
   }
 
   // One dispatch on the check's queue, waited for. Past the deadline, the

@@ -41,6 +41,7 @@
 #include "liveness_kernel.h"
 #include "mi355x/liveness_probe.h"
 #include "probe_json.h"
+#include "probe_request.h"
 
 // defined by the container-emulation builds (native/tools/probe_emu.cpp) only
 extern "C" __attribute__((weak)) const char* mi355x_probe_view_json();
@@ -77,36 +78,18 @@ using mi355x::blank_result;
 using mi355x::datapath_i8_json;
 using mi355x::datapath_json;
 using mi355x::json_escape;
+using mi355x::parse_request;
 using mi355x::perf_json;
+using mi355x::ServeRequest;
 using mi355x::sweep_json;
 
-// phase_us of one device: HSA build = code object, queue, buffers, dispatch;
-// HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch
 #ifdef MI355X_PROBE_HSA
-#define PHASE_NAMES "\"code_object\":%.1f,\"queue\":%.1f,\"buffers\":%.1f,\"dispatch_wait\":%.1f"
+constexpr bool kHsaBuild = true;
 #else
-#define PHASE_NAMES "\"device\":%.1f,\"stream\":%.1f,\"buffers\":%.1f,\"dispatch_wait\":%.1f"
+constexpr bool kHsaBuild = false;
 #endif
 
-std::string device_json(const mi355x_probe_result& r) {
-  char buf[2048];
-  std::snprintf(
-      buf, sizeof(buf),
-      "{\"ordinal\":%d,\"ok\":%s,\"hip_error\":%d,\"mismatches\":%d,\"nonce\":%u,\"xcc_id\":%u,"
-      "\"hw_id\":%u,\"iters\":%d,\"dispatches\":%d,\"kfd_node_id\":%d,\"runtime\":\"%s\","
-      "\"kernel_us\":%.3f,\"setup_us\":%.3f,\"total_us\":%.3f,"
-      "\"phase_us\":{" PHASE_NAMES "},"
-      "\"pci_bus_id\":\"%s\","
-      "\"arch\":\"%s\",\"name\":\"%s\",\"uuid\":\"%s\",\"pci_domain\":%d,\"pci_bus\":%d,"
-      "\"pci_device\":%d,\"cu_count\":%d,\"total_mem\":%llu,\"late\":%s,\"pending_s\":%.3f,\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hip_error, r.mismatches, r.nonce, r.xcc_id, r.hw_id, r.iters,
-      r.dispatches, r.kfd_node_id, r.runtime, r.kernel_us, r.setup_us, r.total_us, r.phase_us[0], r.phase_us[1],
-      r.phase_us[2], r.phase_us[3], json_escape(r.pci_bus_id).c_str(), json_escape(r.arch).c_str(),
-      json_escape(r.name).c_str(), json_escape(r.uuid).c_str(), r.pci_domain, r.pci_bus, r.pci_device,
-      r.cu_count, static_cast<unsigned long long>(r.total_mem), r.late ? "true" : "false", r.pending_s,
-      json_escape(r.error).c_str());
-  return buf;
-}
+std::string device_json(const mi355x_probe_result& r) { return mi355x::device_json(r, kHsaBuild); }
 
 #ifdef MI355X_PROBE_HSA
 int device_count() { return mi355x_hsa_probe_init(); }
@@ -401,70 +384,6 @@ constexpr bool kConcurrentServe = false;  // the HIP build answers in order
 #endif
 constexpr int kMaxServeWorkers = 64;  // beyond this a tagged request is answered inline
 
-struct ServeRequest {
-  bool tagged = false;
-  unsigned long long id = 0;
-  std::string kind;  // probe | sweep | perf | datapath | datapath_i8
-  int iters = 0;
-  double timeout_s = 0;
-  unsigned long long perf_mib = 0;
-  std::vector<int> ords;
-  std::vector<uint32_t> nonces;
-  std::vector<double> timeouts;  // per device
-};
-
-bool parse_request(const std::string& line, ServeRequest* r) {
-  const char* p = line.c_str();
-  if (*p == '@') {
-    char* end = nullptr;
-    r->id = std::strtoull(p + 1, &end, 10);
-    if (end == p + 1 || *end != ' ') return false;
-    r->tagged = true;
-    p = end + 1;
-  }
-  int consumed = 0;
-  bool parsed = false;
-  if (std::strncmp(p, "perf ", 5) == 0) {
-    r->kind = "perf";
-    parsed = std::sscanf(p, "perf %d %lf %llu %n", &r->iters, &r->timeout_s, &r->perf_mib, &consumed) >= 3;
-  } else if (std::strncmp(p, "datapath_i8 ", 12) == 0) {
-    r->kind = "datapath_i8";
-    parsed = std::sscanf(p, "datapath_i8 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath ", 9) == 0) {
-    r->kind = "datapath";
-    parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "sweep ", 6) == 0) {
-    r->kind = "sweep";
-    parsed = std::sscanf(p, "sweep %d %lf %n", &r->iters, &r->timeout_s, &consumed) >= 2;
-  } else if (std::strncmp(p, "probe ", 6) == 0) {
-    r->kind = "probe";
-    parsed = std::sscanf(p, "probe %d %lf %n", &r->iters, &r->timeout_s, &consumed) >= 2;
-  }
-  if (!parsed || consumed == 0) return false;
-  p += consumed;
-  while (*p) {
-    char* end = nullptr;
-    const long o = std::strtol(p, &end, 10);
-    if (end == p || *end != ':') break;
-    p = end + 1;
-    const unsigned long nc = std::strtoul(p, &end, 0);
-    if (end == p) break;
-    p = end;
-    double dl = r->timeout_s;
-    if (*p == ':') {
-      const double v = std::strtod(p + 1, &end);
-      if (end == p + 1) break;
-      if (v > 0) dl = v;
-      p = end;
-    }
-    r->ords.push_back(static_cast<int>(o));
-    r->nonces.push_back(static_cast<uint32_t>(nc));
-    r->timeouts.push_back(dl);
-    while (*p == ' ') ++p;
-  }
-  return true;
-}
-
 std::mutex g_out_mu;
 
 void emit_line(const std::string& s) {
@@ -472,10 +391,6 @@ void emit_line(const std::string& s) {
   std::fputs(s.c_str(), stdout);
   std::fputc('\n', stdout);
   std::fflush(stdout);
-}
-
-std::string id_field(const ServeRequest& r) {
-  return r.tagged ? "\"id\":" + std::to_string(r.id) + "," : std::string();
 }
 
 // One request, start to reply line; then the runtime's deferred frees.
@@ -491,13 +406,7 @@ void answer(const ServeRequest& r, int n) {
     ok = run_batch(r.ords, r.nonces, r.iters, r.timeouts, false, n, results);
     body = devices_json(results);
   }
-  char head[256];
-  std::snprintf(head, sizeof(head), "{%s\"ok\":%s,\"hip_device_count\":%d,\"sweep\":%s,\"perf\":%s,\"t_ready_ns\":%llu,",
-                id_field(r).c_str(), ok ? "true" : "false", n, r.kind == "sweep" ? "true" : "false",
-                r.kind == "perf" ? "true" : "false", static_cast<unsigned long long>(mono_ns()));
-  // only a datapath reply carries its key: the other replies stay as they were
-  const char* key = r.kind == "datapath" ? "\"datapath\":true," : r.kind == "datapath_i8" ? "\"datapath_i8\":true," : "";
-  emit_line(std::string(head) + key + "\"devices\":" + body + "}");
+  emit_line(mi355x::serve_reply_json(r.tagged, r.id, r.kind, ok, n, mono_ns(), body));
   teardown();  // queues/executables go, the runtime (and the kfd process) stays
 }
 
@@ -539,13 +448,7 @@ void serve_worker(ServePool* pool, int n) {
 int serve(int n, uint64_t t_start, uint64_t t_runtime) {
   prctl(PR_SET_PDEATHSIG, SIGKILL);
   if (getppid() == 1) return 0;  // parent already gone
-  char hello[320];
-  std::snprintf(hello, sizeof(hello),
-                "{\"serve\":true,\"ok\":%s,\"hip_device_count\":%d,\"concurrent\":%s,\"deadlines\":true,"
-                "\"t_start_ns\":%llu,\"t_runtime_ns\":%llu}",
-                n >= 0 ? "true" : "false", n < 0 ? 0 : n, kConcurrentServe ? "true" : "false",
-                static_cast<unsigned long long>(t_start), static_cast<unsigned long long>(t_runtime));
-  emit_line(hello);
+  emit_line(mi355x::serve_hello_json(n, kConcurrentServe, t_start, t_runtime));
   if (n < 0) return 2;
   ServePool pool;
   std::vector<std::thread> threads;
@@ -553,12 +456,12 @@ int serve(int n, uint64_t t_start, uint64_t t_runtime) {
   char buf[8192];
   while (std::fgets(buf, sizeof(buf), stdin)) {
     line = buf;
-    while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+    mi355x::strip_eol(&line);
     if (line.empty()) continue;
     if (line == "quit") break;
     ServeRequest r;
     if (!parse_request(line, &r)) {
-      emit_line("{" + id_field(r) + "\"ok\":false,\"error\":\"bad request\",\"devices\":[]}");
+      emit_line(mi355x::bad_request_json(r.tagged, r.id));
       continue;
     }
     bool queued = false;
@@ -722,9 +625,7 @@ int main(int argc, char** argv) {
     return serve(n, t_start, t_runtime);
   }
   if (n < 0) {
-    std::printf("{\"ok\":false,\"hip_device_count\":0,\"error\":\"GPU runtime init failed (%d)\",\"devices\":[],"
-                "\"t_start_ns\":%llu,\"t_ready_ns\":0,\"init_profile\":%s}\n",
-                -n, static_cast<unsigned long long>(t_start), init_profile.c_str());
+    std::printf("%s\n", mi355x::runtime_init_failed_json(-n, t_start, init_profile).c_str());
     return 2;
   }
   std::vector<int> ords;
@@ -749,10 +650,7 @@ int main(int argc, char** argv) {
     const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : datapath_i8_mode ? "datapath_i8" : "sweep";
     std::string body;
     const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
-    std::printf("{\"ok\":%s,\"%s\":true,\"hip_device_count\":%d,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
-                "\"t_ready_ns\":%llu,\"devices\":%s}\n",
-                ok ? "true" : "false", kind, n, static_cast<unsigned long long>(t_start),
-                static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(mono_ns()), body.c_str());
+    std::printf("%s\n", mi355x::oneshot_check_json(kind, ok, n, t_start, t_runtime, mono_ns(), body).c_str());
     std::fflush(stdout);
     return ok ? 0 : 1;
   }
@@ -764,14 +662,11 @@ int main(int argc, char** argv) {
   const bool all_ok = run_batch(ords, nonces, iters, timeouts, identify, n, results);
   const uint64_t t_ready = mono_ns();
   const double cpu_ready = cpu_ms();
-  std::printf("{\"ok\":%s,\"hip_device_count\":%d,\"identify\":%s,\"t_start_ns\":%llu,\"t_runtime_ns\":%llu,"
-              "\"t_ready_ns\":%llu,\"cpu_ms_runtime\":%.2f,\"cpu_user_ms_runtime\":%.2f,\"cpu_ms_ready\":%.2f,\"read_syscalls_runtime\":%lld,"
-              "\"init_us\":{\"dlopen\":%.1f,\"kfd_open\":%.1f,\"hsa_init\":%.1f,\"agents\":%.1f,\"pools\":%.1f},\"init_profile\":%s,"
-              "\"view\":%s,\"devices\":%s}\n",
-              all_ok ? "true" : "false", n, identify ? "true" : "false", static_cast<unsigned long long>(t_start),
-              static_cast<unsigned long long>(t_runtime), static_cast<unsigned long long>(t_ready), cpu_runtime,
-              cpu_user_runtime, cpu_ready, syscr_runtime, iph[0], iph[1], iph[2], iph[3], iph[4], init_profile.c_str(),
-              mi355x_probe_view_json ? view_runtime.c_str() : "null", devices_json(results).c_str());
+  const mi355x::OneshotProbeTimes times = {t_start, t_runtime, t_ready, cpu_runtime, cpu_user_runtime, cpu_ready,
+                                           syscr_runtime, {iph[0], iph[1], iph[2], iph[3], iph[4]}};
+  std::printf("%s\n", mi355x::oneshot_probe_json(all_ok, n, identify, times, init_profile,
+                                                 mi355x_probe_view_json ? view_runtime : "null", devices_json(results))
+                          .c_str());
   std::fflush(stdout);
   // After the verdict. The exit mode was an experiment: the kernel's kfd
   // process teardown after we are gone costs the same either way

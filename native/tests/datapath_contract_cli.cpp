@@ -122,6 +122,7 @@ static int cmd_verdict() {
     auto run = [&] {
       mi355x_datapath_result r;
       std::memset(&r, 0, sizeof(r));
+      r.kfd_node_id = -1;  // records handed over by a test: no agent
       r.nonce = h.nonce;
       r.grid = static_cast<int>(h.grid);
       mi355x::datapath_verdict(records.data(), tiles.data(), h.grid, &r);

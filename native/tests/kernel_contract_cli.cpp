@@ -25,7 +25,7 @@
 //        as above, array 0 = records, 1 = counters.
 //   kernel_contract_cli json sweep|perf I U32 U64 I64 D ERRHEX
 //        the JSON of a result whose every int is I, uint32_t U32, uint64_t U64, int64_t I64, double D
-//        and whose error is the bytes ERRHEX names (at most 159)
+//        and whose error is the bytes ERRHEX names (at most 159), pci_bus_id the first 31 of them
 #include <cinttypes>
 #include <cstddef>
 #include <cstdio>
@@ -207,6 +207,7 @@ static int cmd_sweep_verdict() {
     auto run = [&] {
       mi355x_sweep_result r;
       std::memset(&r, 0, sizeof(r));
+      r.kfd_node_id = -1;  // records handed over by a test: no agent
       r.nonce = h.nonce;
       r.iters = h.iters;
       r.num_xcc = h.num_xcc;
@@ -256,6 +257,7 @@ static int cmd_perf_verdict() {
     auto run = [&] {
       mi355x_perf_result r;
       std::memset(&r, 0, sizeof(r));
+      r.kfd_node_id = -1;  // records handed over by a test: no agent
       r.nonce = h.nonce;
       r.bytes = h.bytes;
       r.num_xcc = h.num_xcc;
@@ -305,17 +307,18 @@ static int cmd_json(int argc, char** argv) {
     mi355x_sweep_result r;
     std::memset(&r, 0, sizeof(r));
     r.ordinal = r.ok = r.hsa_error = r.iters = r.grid = r.cu_count = r.num_xcc = r.records_ok = r.cus_covered =
-        r.xccs_covered = r.all_resident = r.kept_queue = i;
+        r.xccs_covered = r.all_resident = r.kept_queue = r.kfd_node_id = i;
     for (int& w : r.wgs_per_xcc) w = i;
     r.nonce = r.mfma_bad = r.lds_bad = r.tile_bad = u;
     r.kernel_us = r.arrival_spread_us = r.total_us = r.in_flight_s = d;
     set_error(r.error, argv[8]);
+    std::snprintf(r.pci_bus_id, sizeof(r.pci_bus_id), "%s", r.error);
     std::printf("%s\n", mi355x::sweep_json(r).c_str());
   } else if (kind == "perf") {
     mi355x_perf_result r;
     std::memset(&r, 0, sizeof(r));
     r.ordinal = r.ok = r.hsa_error = r.cu_count = r.num_xcc = r.mfma_iters = r.mfma_grid = r.mfma_records_ok =
-        r.mfma_checksum_mismatch = r.mfma_xccs = r.kept_queue = i;
+        r.mfma_checksum_mismatch = r.mfma_xccs = r.kept_queue = r.kfd_node_id = i;
     r.nonce = u;
     r.bytes = r.hbm_bad_words = r.hbm_bad_words_pass2 = u64;
     r.hbm_first_bad = i64;
@@ -323,6 +326,7 @@ static int cmd_json(int argc, char** argv) {
         r.clock_mhz_min = r.clock_mhz_median = r.clock_mhz_max = r.total_us = r.in_flight_s = d;
     for (double& c : r.xcd_clock_mhz) c = d;
     set_error(r.error, argv[8]);
+    std::snprintf(r.pci_bus_id, sizeof(r.pci_bus_id), "%s", r.error);
     std::printf("%s\n", mi355x::perf_json(r).c_str());
   } else {
     return 2;

@@ -393,7 +393,8 @@ class HealthMonitor:
         the partition index in the function bits), so on any mismatch the verdicts of this
         sweep are re-keyed by identity, the ordinal map is rebuilt from the
         replies, and a device no reply identifies loses its ordinal (reported
-        "no HIP device for this ID")."""
+        "no HIP device for this ID"); a reply that names no agent keeps the
+        ordinal it was asked on."""
         idents = {dev: self._reply_identity(o.detail) for dev, o in outcomes.items()}
         bad = sorted(dev for dev in outcomes if not self._identity_matches(dev, idents[dev]))
         if not bad:
@@ -421,6 +422,14 @@ class HealthMonitor:
             if hit is not None and self._identity_matches(dev, self._reply_identity(hit[1].detail)):
                 new_ords[dev] = hit[0]
                 fixed[dev] = hit[1]
+        # a reply that names no agent (it never reached a device, or comes from a
+        # probe that prints no identity) says nothing against its ordinal: the
+        # device keeps it, unless a reply that does name its agent showed whose it is
+        taken = set(new_ords.values())
+        for dev, ordinal in ords.items():
+            if dev not in new_ords and ordinal not in taken and dev in outcomes and idents[dev] is None:
+                new_ords[dev] = ordinal
+                fixed[dev] = outcomes[dev]
         for dev, ordinal in new_ords.items():
             if ords.get(dev) != ordinal:
                 _log.error("probe identity: device %s is ordinal %d, not %s (verdict re-keyed)", dev, ordinal,
@@ -515,6 +524,13 @@ class HealthMonitor:
         REGISTRY.inc("mi355x_dp_perf_checks_total", help="throughput checks run (HBM pattern + MFMA + clocks)")
         for dev, o in res.items():
             d = o.detail or {}
+            if not self._identity_matches(dev, self._reply_identity(d)):
+                # the ordinal map is stale: another agent's verdict is none on this device
+                _log.error("throughput check: reply from agent %s (kfd node %s), not device %s: no verdict this sweep",
+                           d.get("pci_bus_id"), d.get("kfd_node_id"), dev)
+                REGISTRY.inc("mi355x_dp_check_identity_mismatch_total",
+                             help="check replies dropped because another agent than the device's answered", device=dev)
+                continue
             self.perf_last[dev] = d
             if not o.ok:
                 state, why = "failed", f"throughput check: {o.reason}"
@@ -653,7 +669,8 @@ class HealthMonitor:
             every = self.cfg.perf_check_every
             if every > 0 and self.sweeps % every == 0:
                 idle = self._idle_devices(probe_ords)
-                cand = {k: v for k, v in probe_ords.items() if k in idle and self._track[k].live and k in ords}
+                # the ordinals as remapped by this sweep's replies
+                cand = {k: ords[k] for k in probe_ords if k in idle and self._track[k].live and k in ords}
                 if cand:
                     await self._perf_check(cand)
             for dev_id, (state, why) in self._perf.items():

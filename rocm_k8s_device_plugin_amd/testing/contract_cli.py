@@ -1,6 +1,7 @@
 """native/tests/kernel_contract_cli.cpp for the tests: where the built program
 is (or a fresh compile of it), and its sweep-verdict / perf-verdict commands
-as functions of numpy arrays.
+as functions of numpy arrays. Likewise native/tests/probe_contract_cli.cpp
+(the probe's reply printers and request grammar).
 
 A case is what the host was handed after a dispatch; a variant is a list of
 (array, index, value) word replacements applied to the case for one more
@@ -21,6 +22,7 @@ import numpy as np
 
 REPO = Path(__file__).resolve().parent.parent.parent
 SOURCE = REPO / "native" / "tests" / "kernel_contract_cli.cpp"
+PROBE_SOURCE = REPO / "native" / "tests" / "probe_contract_cli.cpp"
 INCLUDES = (REPO / "native" / "include", REPO / "native" / "src" / "health")
 
 RECORDS, TILES, COUNTERS = 0, 1, 1       # a patch's array: sweep (records, tiles), perf (records, counters)
@@ -30,13 +32,13 @@ def host_compiler():
     return os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
 
 
-def compile_cli(exe: Path, extra_flags=()) -> Path:
+def compile_cli(exe: Path, extra_flags=(), source: Path = SOURCE) -> Path:
     cxx = host_compiler()
     assert cxx, "no host C++ compiler"
     cmd = [cxx, "-std=c++17", "-O1", *extra_flags]
     for inc in INCLUDES:
         cmd += ["-I", str(inc)]
-    subprocess.run(cmd + [str(SOURCE), "-o", str(exe)], check=True, timeout=300)
+    subprocess.run(cmd + [str(source), "-o", str(exe)], check=True, timeout=300)
     return exe
 
 
@@ -50,6 +52,33 @@ def contract_cli(build_dir: Path) -> Path:
     if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
         return exe
     return compile_cli(Path(build_dir) / "kernel_contract_cli")
+
+
+def probe_contract_cli(build_dir: Path) -> Path:
+    """native/tests/probe_contract_cli.cpp, found or compiled like contract_cli()."""
+    from .. import _build
+    exe = _build.PROBE_CONTRACT_CLI
+    if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
+        return exe
+    return compile_cli(Path(build_dir) / "probe_contract_cli", source=PROBE_SOURCE)
+
+
+def probe_replies_text(cli) -> str:
+    """The document `probe_contract_cli replies` prints, as its bytes."""
+    r = subprocess.run([str(cli), "replies"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    return r.stdout
+
+
+def probe_parse(cli, lines) -> list:
+    """`probe_contract_cli parse` over request lines (each with its own line
+    end or none): per line the parsed request, or "bad request"."""
+    text = "".join(ln if ln.endswith("\n") else ln + "\n" for ln in lines)
+    r = subprocess.run([str(cli), "parse"], input=text.encode(), capture_output=True, timeout=60)
+    assert r.returncode == 0, (r.returncode, r.stderr.decode(errors="replace")[-3000:])
+    out = [json.loads(ln) for ln in r.stdout.decode().splitlines()]
+    assert len(out) == len(lines), (len(out), len(lines))
+    return out
 
 
 def _variants_blob(variants) -> bytes:

@@ -380,6 +380,7 @@ def verdict(records, tiles, grid: int, nonce: int) -> dict:
         "first_bad_got": 0, "first_bad_want": 0, "first_bad_xor": 0,
         "cus_covered": len(cus), "simds_covered": len(simds), "xccs_covered": len(set(xccs)),
         "ok": records_ok == grid,
+        "kfd_node_id": -1, "pci_bus_id": "",        # a verdict on records alone names no agent (hsa_chip.cpp does)
     }
     if first:
         wg, w = first

@@ -493,6 +493,12 @@ def _median(values) -> float:
     return sorted(values)[len(values) // 2] if values else 0.0
 
 
+# The verdict judges records; which agent wrote them is the caller's to say
+# (hsa_chip.cpp fills kfd_node_id and pci_bus_id once it has reached the
+# device). A verdict on records alone carries "no agent".
+NO_AGENT = {"kfd_node_id": -1, "pci_bus_id": ""}
+
+
 def sweep_verdict(records, tiles, grid: int, nonce: int, iters: int, num_xcc: int) -> dict:
     rec = np.asarray(records, dtype=np.uint32).reshape(grid, REC_WORDS).astype(np.uint64)
     got = _bits(np.asarray(tiles, dtype=np.float32)).reshape(grid, PROBE_M * PROBE_N)
@@ -520,6 +526,7 @@ def sweep_verdict(records, tiles, grid: int, nonce: int, iters: int, num_xcc: in
         "arrival_spread_us": (max(arrivals) - min(arrivals)) / REALTIME_MHZ if arrivals else 0.0,
     }
     out["ok"] = records_ok == grid and (num_xcc <= 0 or out["xccs_covered"] == num_xcc)
+    out.update(NO_AGENT)
     return out
 
 
@@ -565,6 +572,7 @@ def perf_verdict(records, counters, burn_wgs: int, nonce: int, num_xcc: int, byt
     }
     out["ok"] = (out["hbm_bad_words"] == 0 and mismatch == 0 and len(present) == burn_wgs
                  and (num_xcc <= 0 or len(xccs) == num_xcc))
+    out.update(NO_AGENT)
     return out
 
 

@@ -309,6 +309,128 @@ def test_probe_identity_rekeys_verdicts(tmp_path, mode):
         eng.close()
 
 
+def _reversed_agents(tmp_path, fi):
+    """(inv, order, identity env): the agent at ordinal i is really device
+    order[n-1-i], where order is the positional map's."""
+    inv = discover(str(fi.sysfs))
+    ctl, eng = _engine(fi, tmp_path, {})
+    pos = eng.ordinals()
+    eng.close()
+    n = len(pos)
+    order = sorted(pos, key=pos.get)
+    ident = {str(i): {"kfd_node_id": inv.by_id[order[n - 1 - i]].node_id,
+                      "pci_bus_id": _bus_id(inv.by_id[order[n - 1 - i]])} for i in range(n)}
+    return inv, order, {"MI355X_STUB_PROBE_IDENTITY": json.dumps(ident)}
+
+
+@pytest.mark.parametrize("busy", [(), (0, 1, 6)], ids=["all_idle", "idle_and_busy"])
+def test_probe_identity_rekeys_verdicts_on_a_chip_sweep_pulse(tmp_path, busy):
+    """The same with the chip sweep due on that pulse: idle GPUs answer with a
+    sweep reply (which names its agent as a probe reply does), busy ones with a
+    probe reply. The failing agent's verdict lands on its own kubelet ID, the
+    map is rebuilt, and no device loses its ordinal."""
+    fi = make_mi355x_node(tmp_path / "n")
+    inv, order, env = _reversed_agents(tmp_path, fi)
+    n = len(order)
+    for i in busy:
+        _busy_gpu(fi, inv, order[i], pid=str(700 + i))
+    iters_log = tmp_path / "iters.log"
+    env["MI355X_STUB_PROBE_ITERS_LOG"] = str(iters_log)
+    ctl, eng = _engine(fi, tmp_path, {"3": "fail"}, env=env, fail_threshold=1, chip_sweep_every=1,
+                       busy_grace_s=300.0)
+    eng.set_activity({})
+    try:
+        eng.sweep()
+        assert _unhealthy(eng) == {order[n - 1 - 3]}, eng.snapshot()
+        eng.sweep()
+        snap = eng.snapshot()
+        assert _unhealthy(eng) == {order[n - 1 - 3]}, snap
+        assert not any("no HIP device" in r for _, rs in snap.values() for r in rs), snap
+        assert "tile_bad=1" in snap[order[n - 1 - 3]][1][0]            # agent 3 is idle: a sweep's verdict
+        assert eng.ordinals() == {order[n - 1 - i]: i for i in range(n)}
+        assert eng.stats()["identity_remaps"] == 1 and eng.stats()["chip_sweeps"] == 2
+        kinds = {ln.split()[0] for ln in iters_log.read_text().splitlines()}
+        assert kinds == ({"sweep", "probe"} if busy else {"sweep"})
+    finally:
+        eng.close()
+
+
+def test_a_reply_that_names_no_agent_keeps_its_ordinal_through_a_rekey(tmp_path):
+    """Two busy GPUs answer from each other's agents, so the pulse re-keys; an
+    idle, healthy GPU's sweep reply names no agent (a probe that prints none,
+    or a reply that never reached the device). It says nothing against its
+    ordinal: the device keeps it and stays Healthy."""
+    fi = make_mi355x_node(tmp_path / "n")
+    inv = discover(str(fi.sysfs))
+    ctl, eng = _engine(fi, tmp_path, {})
+    pos = eng.ordinals()
+    eng.close()
+    dev = {o: d for d, o in pos.items()}
+    truly = {0: 1, 1: 0}                                                # ordinal -> the ordinal whose device answers
+    ident = {str(o): {"kfd_node_id": inv.by_id[dev[truly.get(o, o)]].node_id,
+                      "pci_bus_id": _bus_id(inv.by_id[dev[truly.get(o, o)]])} for o in pos.values() if o != 5}
+    for o in (0, 1):
+        _busy_gpu(fi, inv, dev[o], pid=str(700 + o))
+    ctl, eng = _engine(fi, tmp_path, {}, env={"MI355X_STUB_PROBE_IDENTITY": json.dumps(ident)}, fail_threshold=1,
+                       chip_sweep_every=1, busy_grace_s=300.0)
+    eng.set_activity({})
+    try:
+        eng.sweep()
+        assert eng.stats()["identity_remaps"] == 1
+        assert _unhealthy(eng) == set(), eng.snapshot()
+        assert eng.ordinals() == {**pos, dev[0]: 1, dev[1]: 0}
+    finally:
+        eng.close()
+
+
+CHECK_FAULTS = [("perf", "corrupt", "perf_check_every", "hbm_bad_words=3"),
+                ("datapath", "stuck_bit", "datapath_check_every", "stage 2 word 5"),
+                ("datapath_i8", "device_bad", "datapath_i8_check_every", "device_bad=12")]
+
+
+@pytest.mark.parametrize("kind,mode,every,says", CHECK_FAULTS, ids=[c[0] for c in CHECK_FAULTS])
+def test_a_check_verdict_lands_on_the_device_its_agent_is(tmp_path, kind, mode, every, says):
+    """Agents enumerated in reverse order, a failing check on agent 3: its
+    verdict persists, so it may land on the device agent 3 really is, or on no
+    device in that pulse, never on another one."""
+    fi = make_mi355x_node(tmp_path / "n")
+    inv, order, env = _reversed_agents(tmp_path, fi)
+    n = len(order)
+    ctl, eng = _engine(fi, tmp_path, {kind: {"3": mode}}, env=env, fail_threshold=1, **{every: 1})
+    try:
+        for pulse in range(2):
+            eng.sweep()
+            assert _unhealthy(eng) <= {order[n - 1 - 3]}, (pulse, eng.snapshot())
+        assert _unhealthy(eng) == {order[n - 1 - 3]}
+        assert says in " ".join(eng.snapshot()[order[n - 1 - 3]][1])
+        assert eng.ordinals() == {order[n - 1 - i]: i for i in range(n)}
+    finally:
+        eng.close()
+
+
+def test_a_check_reply_from_another_agent_is_no_verdict(tmp_path):
+    """The map is stale where no probe reply shows it (the probes of ordinals
+    2 and 3 name no agent), but the check replies name theirs: agent 3's failed
+    datapath check is dropped, not written to the device the map puts at 3."""
+    fi = make_mi355x_node(tmp_path / "n")
+    inv = discover(str(fi.sysfs))
+    ctl, eng = _engine(fi, tmp_path, {})
+    pos = eng.ordinals()
+    eng.close()
+    ident = {str(o): {"kfd_node_id": inv.by_id[d].node_id, "pci_bus_id": _bus_id(inv.by_id[d])} for d, o in pos.items()}
+    ident["2"], ident["3"] = ident["3"], ident["2"]                    # agents 2 and 3 are each other's devices
+    env = {"MI355X_STUB_PROBE_IDENTITY": json.dumps(ident), "MI355X_STUB_PROBE_ANONYMOUS": "probe"}
+    ctl, eng = _engine(fi, tmp_path, {"datapath": {"3": "stuck_bit"}}, env=env, fail_threshold=1,
+                       datapath_check_every=1)
+    try:
+        eng.sweep()
+        assert eng.stats()["identity_remaps"] == 0
+        assert _unhealthy(eng) == set(), eng.snapshot()                 # neither dev[3] nor dev[2]
+        assert eng.stats()["datapath_checks"] == 1 and eng.stats()["datapath_failures"] == 0
+    finally:
+        eng.close()
+
+
 def test_probe_identity_unmatched_device_loses_its_ordinal(tmp_path):
     fi = make_mi355x_node(tmp_path / "n")
     inv = discover(str(fi.sysfs))

@@ -1095,6 +1095,123 @@ def test_probe_identity_rekeys_verdicts(tmp_path, mode):
     assert mon.identity_remaps == 1                   # second sweep already used the rebuilt map
 
 
+def _reversed_monitor(tmp_path, control, busy=(), anonymous=None, **cfg):
+    """(inv, monitor) where the plugin's ordinal map is the reverse of what ROCr
+    enumerates: the agent at ordinal i is inv.devices[i], the map says n-1-i."""
+    fi = make_mi355x_node(tmp_path / "n")
+    inv = discover(str(fi.sysfs))
+    n = len(inv.devices)
+    wrong = {d.id: n - 1 - i for i, d in enumerate(inv.devices)}
+    ident = {str(i): {"kfd_node_id": d.node_id, "pci_bus_id": _bus_id(d)} for i, d in enumerate(inv.devices)}
+    for i in busy:
+        _busy_gpu(fi, inv, inv.devices[i].id, pid=str(700 + i))
+    ctl, prober = _stub_prober(tmp_path, control)
+    prober.extra_env["MI355X_STUB_PROBE_IDENTITY"] = json.dumps(ident)
+    if anonymous:
+        prober.extra_env["MI355X_STUB_PROBE_ANONYMOUS"] = anonymous
+    prober.kfd_proc_dir = str(fi.sysfs / "class/kfd/kfd/proc")
+    mon = HealthMonitor(inv, HealthConfig(exporter_socket=None, liveness=True, fail_threshold=1,
+                                          liveness_busy_grace_s=300.0, **cfg), prober=prober, ordinal_map=wrong)
+    return inv, mon
+
+
+@pytest.mark.parametrize("busy", [(), (0, 1, 6)], ids=["all_idle", "idle_and_busy"])
+def test_probe_identity_rekeys_verdicts_on_a_chip_sweep_pulse(tmp_path, busy):
+    """The same with the chip sweep due on that pulse: idle GPUs answer with a
+    sweep reply (which names its agent as a probe reply does), busy ones with a
+    probe reply. The failing agent's verdict lands on its own kubelet ID, the
+    map is rebuilt, and no device loses its ordinal."""
+    inv, mon = _reversed_monitor(tmp_path, {"3": "fail"}, busy=busy, chip_sweep_every=1)
+
+    async def go():
+        try:
+            await mon.check_once()
+            first = {d.id for d in inv.devices if mon.health(d.id) == "Unhealthy"}
+            await mon.check_once()
+            return first
+        finally:
+            await mon.close()
+
+    first = run(go(), timeout=60)
+    bad = inv.devices[3].id
+    assert first == {bad}
+    assert {d.id for d in inv.devices if mon.health(d.id) == "Unhealthy"} == {bad}
+    assert not any("no HIP device" in r for v in mon.snapshot().values() for r in v.reasons)
+    assert "tile_bad=1" in mon.snapshot()[bad].reasons[0]                  # agent 3 is idle: a sweep's verdict
+    assert mon.ordinals() == {d.id: i for i, d in enumerate(inv.devices)}
+    assert mon.identity_remaps == 1 and mon.chip_sweeps == 2
+
+
+def test_a_reply_that_names_no_agent_keeps_its_ordinal_through_a_rekey(tmp_path):
+    """Two busy GPUs answer from each other's agents, so the pulse re-keys; the
+    idle GPUs' sweep replies name no agent (a probe that prints none). They say
+    nothing against their ordinals: those devices keep them and stay Healthy."""
+    fi = make_mi355x_node(tmp_path / "n")
+    inv = discover(str(fi.sysfs))
+    truth = {d.id: i for i, d in enumerate(inv.devices)}
+    wrong = {**truth, inv.devices[0].id: 1, inv.devices[1].id: 0}
+    ident = {str(i): {"kfd_node_id": d.node_id, "pci_bus_id": _bus_id(d)} for i, d in enumerate(inv.devices)}
+    for i in (0, 1):
+        _busy_gpu(fi, inv, inv.devices[i].id, pid=str(700 + i))
+    ctl, prober = _stub_prober(tmp_path, {})
+    prober.extra_env.update(MI355X_STUB_PROBE_IDENTITY=json.dumps(ident), MI355X_STUB_PROBE_ANONYMOUS="sweep")
+    prober.kfd_proc_dir = str(fi.sysfs / "class/kfd/kfd/proc")
+    mon = HealthMonitor(inv, HealthConfig(exporter_socket=None, liveness=True, fail_threshold=1, chip_sweep_every=1,
+                                          liveness_busy_grace_s=300.0), prober=prober, ordinal_map=wrong)
+
+    async def go():
+        try:
+            await mon.check_once()
+        finally:
+            await mon.close()
+
+    run(go(), timeout=60)
+    assert mon.identity_remaps == 1 and mon.chip_sweeps == 1
+    assert all(mon.health(d.id) == "Healthy" for d in inv.devices), mon.snapshot()
+    assert mon.ordinals() == truth
+
+
+def test_a_check_verdict_lands_on_the_device_its_agent_is(tmp_path):
+    """Agents enumerated in reverse order, a failing throughput check on agent
+    3: its verdict persists, so it may land on the device agent 3 really is, or
+    on no device in that pulse, never on another one."""
+    inv, mon = _reversed_monitor(tmp_path, {"perf": {"3": "corrupt"}}, perf_check_every=1)
+    bad = inv.devices[3].id
+    seen = []
+
+    async def go():
+        try:
+            for _ in range(2):
+                await mon.check_once()
+                seen.append({d.id for d in inv.devices if mon.health(d.id) == "Unhealthy"})
+        finally:
+            await mon.close()
+
+    run(go(), timeout=60)
+    assert all(s <= {bad} for s in seen) and seen[-1] == {bad}, seen
+    assert "hbm_bad_words=3" in " ".join(mon.snapshot()[bad].reasons)
+    assert set(d for d, (state, _) in mon.perf_verdicts().items() if state != "ok") == {bad}
+    assert mon.ordinals() == {d.id: i for i, d in enumerate(inv.devices)}
+
+
+def test_a_check_reply_from_another_agent_is_no_verdict(tmp_path):
+    """The map is stale where no probe reply shows it (the probes name no
+    agent), but the check replies name theirs: agent 3's failed throughput check
+    is dropped, not written to the device the map puts at ordinal 3."""
+    inv, mon = _reversed_monitor(tmp_path, {"perf": {"3": "corrupt"}}, anonymous="probe", perf_check_every=1)
+
+    async def go():
+        try:
+            await mon.check_once()
+        finally:
+            await mon.close()
+
+    run(go(), timeout=60)
+    assert mon.identity_remaps == 0 and mon.perf_checks == 1
+    assert all(mon.health(d.id) == "Healthy" for d in inv.devices), mon.snapshot()
+    assert mon.perf_verdicts() == {}
+
+
 def test_probe_identity_unmatched_device_loses_its_ordinal(tmp_path):
     """A reply from an agent no advertised device corresponds to: the device
     the verdict was meant for is reported without a HIP device, not Healthy."""

@@ -33,8 +33,9 @@ SWEEP_ZERO_KEYS = {"ordinal": 0, "hsa_error": 0, "cu_count": 0, "kernel_us": 0, 
                    "kept_queue": False}
 PERF_ZERO_KEYS = {"ordinal": 0, "hsa_error": 0, "cu_count": 0, "total_us": 0, "in_flight_s": 0, "kept_queue": False}
 
-# the probe's format strings before the JSON was built without a fixed buffer: the expectation of
-# test_json_line_is_byte_identical_to_the_fixed_buffer_format, not used by the product
+# the probe's format strings before the JSON was built without a fixed buffer (and before a check's
+# reply named its agent): the expectation of test_json_line_is_byte_identical_to_the_fixed_buffer_format,
+# not used by the product
 OLD_SWEEP_FORMAT = ("{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"iters\":%d,\"grid\":%d,"
                     "\"cu_count\":%d,\"num_xcc\":%d,\"records_ok\":%d,\"mfma_bad\":%u,\"lds_bad\":%u,"
                     "\"tile_bad\":%u,\"cus_covered\":%d,\"xccs_covered\":%d,\"all_resident\":%s,"
@@ -445,17 +446,25 @@ def _json_bool(b):
     return "true" if b else "false"
 
 
+def _without_identity(line):
+    """The line as it was before a check's reply named its agent: the two keys
+    in front of "error", which a verdict on records alone leaves at -1 and ""."""
+    key = ",\"kfd_node_id\":-1,\"pci_bus_id\":\"\",\"error\":"
+    assert line.count(key) == 1, line[-200:]
+    return line.replace(key, ",\"error\":")
+
+
 def test_json_line_is_byte_identical_to_the_fixed_buffer_format(corpus, lines):
     w = corpus["sweep256"].reference()
     per = "[" + ",".join(str(x) for x in w["wgs_per_xcc"]) + "]"
-    assert lines.by_case["sweep256"][0] == _c_format(OLD_SWEEP_FORMAT, [
+    assert _without_identity(lines.by_case["sweep256"][0]) == _c_format(OLD_SWEEP_FORMAT, [
         0, _json_bool(w["ok"]), 0, w["nonce"], w["iters"], w["grid"], 0, w["num_xcc"], w["records_ok"], w["mfma_bad"],
         w["lds_bad"], w["tile_bad"], w["cus_covered"], w["xccs_covered"], _json_bool(w["all_resident"]), per, 0.0,
         w["arrival_spread_us"], 0.0, 0.0, "false", ""])
     for name in ("burn512", "burn_clocks_16_xcds"):
         w = corpus[name].reference()
         per = "[" + ",".join("%.0f" % x for x in w["xcd_clock_mhz"]) + "]"
-        assert lines.by_case[name][0] == _c_format(OLD_PERF_FORMAT, [
+        assert _without_identity(lines.by_case[name][0]) == _c_format(OLD_PERF_FORMAT, [
             0, _json_bool(w["ok"]), 0, w["nonce"], w["bytes"], 0, w["num_xcc"], w["fill_us"], w["check_us"],
             w["check2_us"], w["hbm_write_gbps"], w["hbm_read_gbps"], w["hbm_bad_words"], w["hbm_bad_words_pass2"],
             w["hbm_first_bad"], w["mfma_iters"], w["mfma_grid"], w["mfma_records_ok"], w["mfma_checksum_mismatch"],
@@ -492,6 +501,7 @@ def test_json_line_with_every_field_at_its_widest_is_whole(cli, kind):
                        "total_us", "in_flight_s")}[kind]
     assert all(d[k] == WIDE["i"] for k in ints) and all(d[k] == 1e15 for k in floats)
     assert d["nonce"] == WIDE["u32"] and d["ok"] is True and d["kept_queue"] is True
+    assert d["kfd_node_id"] == WIDE["i"] and d["pci_bus_id"] == WIDE_ERROR[:31].decode()
     if kind == "sweep":
         assert d["mfma_bad"] == d["lds_bad"] == d["tile_bad"] == WIDE["u32"] and d["all_resident"] is True
         assert d["wgs_per_xcc"] == [WIDE["i"]] * 8
