@@ -123,9 +123,11 @@ class LivenessProber {
   //      budget;
   //   3. a fresh process for each GPU the server failed or could not answer
   //      for (a pending one only where idle), while at least 1 s is left.
-  // Whatever the budget leaves unsettled comes back pending. Never starts,
-  // restarts or stops the server; a failure a fresh process does not confirm
-  // asks the next sweep to restart it. Leaves the sweep's backoff and counters alone.
+  // Whatever the budget leaves unsettled comes back pending, and a request
+  // whose deadline the budget no longer covers is not sent at all. Never starts,
+  // restarts or stops the server; a definite failure (not a pending answer) a
+  // fresh process does not confirm asks the next sweep to restart it. Leaves
+  // the sweep's backoff and counters alone.
   std::map<int, ProbeOutcome> check(const std::vector<int>& ordinals, const std::function<std::set<int>()>& busy_of,
                                     double budget_s);
   // restrict the server to these host ordinals (nullopt = all); a change restarts it
@@ -161,7 +163,10 @@ class LivenessProber {
   std::shared_ptr<Server> server_;
   int backoff_ = 0;
   bool restart_wanted_ = false;
-  // ordinal -> nonces of probe dispatches that may still answer late (kept slot)
+  // ordinal -> nonces of the probe requests sent to server_ since the device's
+  // kept slot was last known clear, oldest first: one of them is the dispatch a
+  // late verdict answers. Recorded when the line is written; cleared by a reply
+  // that shows the slot clear (a late verdict included) and with the server.
   std::map<int, std::vector<uint32_t>> issued_;
   std::optional<std::vector<int>> visible_;
   std::atomic<uint64_t> next_id_{1};

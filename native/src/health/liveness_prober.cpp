@@ -236,6 +236,21 @@ ProbeOutcome judge(bool doc_ok, const json::Value* d, uint32_t nonce, double ms,
   return o;
 }
 
+// A probe nonce sent for a device since its kept slot was last known clear
+// (LivenessProber::issued_). The dispatch a late verdict answers was submitted
+// by one of the first requests after that moment, so the oldest entries are
+// the ones that matter and are never evicted while newer ones stay: a full
+// list drops the oldest entry of its newer half. (The newer half is for the
+// slot that cleared in a reply this prober dropped: the next dispatch's nonce
+// is then a recent one.)
+constexpr size_t kMaxIssued = 64;
+
+void remember_nonce(std::vector<uint32_t>* sent, uint32_t nonce) {
+  if (std::find(sent->begin(), sent->end(), nonce) != sent->end()) return;
+  if (sent->size() >= kMaxIssued) sent->erase(sent->begin() + kMaxIssued / 2);
+  sent->push_back(nonce);
+}
+
 std::string join_ints(const std::vector<int>& v, const char* sep) {
   std::string s;
   for (size_t i = 0; i < v.size(); ++i) s += (i ? sep : "") + std::to_string(v[i]);
@@ -668,6 +683,13 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
     std::snprintf(tok, sizeof(tok), " %d:%u:%.3f", local[o], nonces[o], deadlines.at(o));
     line += tok;
   }
+  if (kind == "probe") {
+    // recorded before the line is written: the reply may be dropped at
+    // wait_until, and the dispatch it left on the kept slot still answers late
+    std::lock_guard<std::mutex> lk(mu_);
+    if (server_ == s)
+      for (int o : uniq) remember_nonce(&issued_[o], nonces[o]);
+  }
   std::string reply;
   const Got g = transact(s, line, wait_until, &reply);
   if (g != Got::kLine) {
@@ -691,6 +713,9 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
     }
   std::map<int, ProbeOutcome> out;
   std::lock_guard<std::mutex> lk(mu_);  // issued_
+  // issued_ belongs to the current server: a reply from one that was replaced
+  // meanwhile neither reads nor changes it
+  const bool current = server_ == s;
   for (int o : uniq) {
     auto it = by_ord.find(o);
     if (it == by_ord.end()) {
@@ -702,34 +727,37 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
     }
     const json::Value* d = it->second;
     const bool timed_out = jnum(d, "hip_error", 0) == -1 || jnum(d, "hsa_error", 0) == -1;
-    if (kind != "probe") {  // sweeps run on their own queue: the kept slot is untouched
+    if (kind != "probe") {
+      // sweeps and checks borrow the kept queue (hsa_chip.cpp, DeviceWork::open) but neither
+      // collect nor replace a probe's outstanding dispatch: issued_ stays as it is
       out[o] = judge(jbool(d, "ok"), d, nonces[o], ms);
       out[o].queue_lost = timed_out && !cfg_.keep_queues;
       continue;
     }
-    // a late verdict answers the dispatch (and nonce) of an earlier request that left it pending
-    auto& mine = issued_[o];
+    // A late verdict answers the dispatch (and nonce) of an earlier request
+    // that left it pending. It is accepted only against a nonce this prober
+    // sent to this server for this device since the slot was last clear.
+    std::vector<uint32_t> none;
+    auto& mine = current ? issued_[o] : none;
     const bool late = jbool(d, "late");
     uint32_t expect = nonces[o];
     if (late) {
       const json::Value* n = d->get("nonce");
       const uint32_t got = n && n->kind == json::Value::Number
                                ? static_cast<uint32_t>(std::strtoull(n->s.c_str(), nullptr, 10)) : 0;
-      if (auto f = std::find(mine.begin(), mine.end(), got); f != mine.end()) {
-        expect = got;
-        mine.erase(f);
-      }
+      if (std::find(mine.begin(), mine.end(), got) != mine.end()) expect = got;
     }
     ProbeOutcome r = judge(jbool(d, "ok"), d, expect, ms);
     r.queue_lost = timed_out && !cfg_.keep_queues;
     if (!r.ok && jnum(d, "pending_s", 0) > 0) {
       r.pending = true;
-      mine.push_back(nonces[o]);  // may be the dispatch still queued on the kept slot
-      if (mine.size() > 8) mine.erase(mine.begin());
+      // again, if another request's reply showed the slot clear after this one was
+      // sent: this one may have submitted the dispatch that is outstanding now
+      remember_nonce(&mine, nonces[o]);
     } else if (!r.ok && jnum(d, "hip_error", 0) == -1 && !cfg_.keep_queues) {
       r.pending = true;  // timed out without a kept slot: no late verdict will follow
-    } else if (!late) {
-      mine.clear();  // the slot had nothing outstanding
+    } else {
+      mine.clear();  // a verdict, late or its own: the slot has nothing outstanding now
     }
     out[o] = r;
   }
@@ -865,6 +893,9 @@ std::map<int, ProbeOutcome> LivenessProber::check(const std::vector<int>& ordina
   }
   bool interrupted = false;
   auto ask = [&](const std::vector<int>& ords, double deadline) {
+    // what is left of the budget does not cover the server's deadline: its reply
+    // would be dropped, and a dispatch left on a busy GPU's slot collected by nobody
+    if (end - mono_s() < deadline) return std::map<int, ProbeOutcome>{};
     std::map<int, double> dl;
     for (int o : ords) dl[o] = deadline;
     std::string err;
@@ -942,7 +973,9 @@ std::map<int, ProbeOutcome> LivenessProber::check(const std::vector<int>& ordina
     ProbeOutcome f = fresh[o];
     const bool server_failed = got.count(o) && !got[o].ok;
     if (f.ok) {
-      if (server_failed) {
+      // a pending answer is no failure: the server's own chip sweep or
+      // throughput check may hold the device's slot for its whole run
+      if (server_failed && !got[o].pending) {
         std::lock_guard<std::mutex> lk(mu_);
         restart_wanted_ = true;  // a stale server runtime: the next sweep restarts it
       }

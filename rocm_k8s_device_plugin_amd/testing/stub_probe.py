@@ -35,6 +35,14 @@ follow the "datapath_i8" map with the same modes; each one appends
 "datapath_i8:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
+Every line --serve reads and every line it writes back is appended to
+$MI355X_STUB_PROBE_REQUEST_LOG if set, as "> <request line>" and "< <reply>":
+what reached the server and what it said, whether or not the caller still
+waited for it. The log changes no reply.
+Two control keys are for the prober's late-verdict bookkeeping alone:
+"reply_delay_s" holds every --serve reply back that long (a reply its caller has
+stopped waiting for), and "late_nonce" ({ordinal: nonce}) makes the device's next
+verdicts late ones that carry that nonce (a dispatch this server never got).
 """
 import json
 import os
@@ -241,6 +249,13 @@ def _kfd_entry():
     return entry
 
 
+def _log_wire(mark, text):
+    path = os.environ.get("MI355X_STUB_PROBE_REQUEST_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"{mark} {text}\n")
+
+
 def _log_iters(kind, iters):
     path = os.environ.get("MI355X_STUB_PROBE_ITERS_LOG")
     if path:
@@ -336,8 +351,8 @@ def serve():
     # like the real server: tagged requests are answered concurrently, as they complete
     print(json.dumps({"serve": True, "ok": True, "hip_device_count": 8, "concurrent": True, "deadlines": True,
                       "t_start_ns": t, "t_runtime_ns": t}), flush=True)
-    slots = {}   # ordinal -> nonce of the kept slot's outstanding dispatch (like --keep)
-    slow = {}    # ordinal -> (submitted at, nonce) of a "slow" device's outstanding dispatch
+    slots = {}   # ordinal -> (nonce, iters) of the kept slot's outstanding dispatch (like --keep)
+    slow = {}    # ordinal -> (submitted at, nonce, iters) of a "slow" device's outstanding dispatch
     flying = {}  # ordinal -> when a sweep that did not complete was submitted (at most one per device)
     locks = {}   # ordinal -> its kept slot's lock (requests on one device serialise, as on the real server)
     out_mu, state_mu = threading.Lock(), threading.Lock()
@@ -410,7 +425,7 @@ def serve():
             # a request whose deadline comes first is answered pending (the
             # dispatch stays queued), and a later one collects its late verdict
             with state_mu:
-                since, first = slow.setdefault(o, (time.monotonic(), n))
+                since, first, first_iters = slow.setdefault(o, (time.monotonic(), n, iters))
             left = since + float(ctl.get("slow_s", 1.0)) - time.monotonic()
             if left > deadline:
                 time.sleep(deadline)
@@ -421,7 +436,8 @@ def serve():
             time.sleep(max(0.0, left))
             with state_mu:
                 slow.pop(o, None)
-            d = _device(o, "ok", first, host_ordinal=int(hosto), iters=iters)
+            # the verdict names the dispatch it is about: its nonce and its iteration count
+            d = _device(o, "ok", first, host_ordinal=int(hosto), iters=first_iters)
             d["late"] = first != n
             return d
         if mode == "timeout":   # server without kept queues: the dispatch did not complete
@@ -434,7 +450,7 @@ def serve():
             # server waits out this device's whole deadline first, as
             # hsa_probe.cpp's wait_and_verify does
             with state_mu:
-                slots.setdefault(o, n)
+                slots.setdefault(o, (n, iters))
             if starts_log:   # a test can tell when a request is waiting on this device
                 with open(starts_log, "a") as f:
                     f.write(f"pending:{hosto}\n")
@@ -445,8 +461,10 @@ def serve():
             return d
         with state_mu:
             late = slots.pop(o, None)
+        if late is None and hosto in ctl.get("late_nonce", {}):
+            late = (int(ctl["late_nonce"][hosto]), iters)
         if late is not None:   # the outstanding dispatch completed: its late verdict
-            d = _device(o, mode, late, host_ordinal=int(hosto), iters=iters)
+            d = _device(o, mode, late[0], host_ordinal=int(hosto), iters=late[1])
             d["late"] = True
             return d
         return _device(o, mode, n, host_ordinal=int(hosto), iters=iters)
@@ -481,7 +499,9 @@ def serve():
             th.join()
         # like the real server: a request that names no device is not ok
         doc = _envelope(kind, bool(res) and all(d["ok"] for d in res), 8, res, req["id"] if req["tagged"] else None)
+        time.sleep(float(ctl.get("reply_delay_s", 0)))
         with out_mu:
+            _log_wire("<", json.dumps(doc))
             sys.stdout.write(json.dumps(doc) + "\n")
             sys.stdout.flush()
 
@@ -490,11 +510,13 @@ def serve():
         line = line.rstrip("\r\n")
         if not line:
             continue
+        _log_wire(">", line)
         if line == "quit":
             break
         req, tagged, rid = _parse_tagged(line)
         if req is None:      # the real server says so and goes on
             with out_mu:
+                _log_wire("<", json.dumps(_bad_request(tagged, rid)))
                 sys.stdout.write(json.dumps(_bad_request(tagged, rid)) + "\n")
                 sys.stdout.flush()
             continue
