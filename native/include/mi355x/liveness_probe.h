@@ -306,6 +306,20 @@ int mi355x_hsa_datapath_i8_check(int ordinal, uint32_t nonce, double timeout_s, 
 // `ordinal` (-1 = all devices) before the verdict; stage < 0 = off.
 void mi355x_hsa_datapath_i8_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- bf16 MFMA datapath check (128-bit operands, bit-exact) -------------------
+// The same shape again, on the instructions pods mostly run: four
+// v_mfma_f32_32x32x16_bf16 stages and one v_mfma_f32_16x16x32_bf16 stage per
+// wave, with operands chosen so that every product and every partial sum, in
+// any order, is an exact f32 (datapath_bf16_kernel.h). Each wave checks its
+// accumulators, as words, against a VALU fmaf recomputation; the host checks
+// wave 0's five tiles of every workgroup word for word. The result has the
+// int8 check's fields with the same meaning (mfma_bad counts f32 words).
+typedef mi355x_datapath_i8_result mi355x_datapath_bf16_result;
+
+int mi355x_hsa_datapath_bf16_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_bf16_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later bf16 check.
+void mi355x_hsa_datapath_bf16_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

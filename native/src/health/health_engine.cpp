@@ -488,7 +488,7 @@ void Engine::judge_liveness(const std::map<std::string, ProbeOutcome>& outcomes,
   }
 }
 
-// what tells the two MFMA datapath checks apart (Engine::datapath_check)
+// what tells the MFMA datapath checks apart (Engine::datapath_check)
 struct Engine::DatapathKind {
   const char* verb;    // the prober's request
   const char* label;   // in reasons and log lines
@@ -507,6 +507,10 @@ const Engine::DatapathKind Engine::kDatapathI8 = {
     "datapath_i8", "datapath i8 check", "health.datapath_i8_check", "mi355x_dp_datapath_i8_checks_total",
     "int8 MFMA datapath checks run (128-bit operands, bit-exact, on the idle GPUs)",
     "mi355x_dp_datapath_i8_check_failures_total", "int8 MFMA datapath checks that did not pass"};
+const Engine::DatapathKind Engine::kDatapathBf16 = {
+    "datapath_bf16", "datapath bf16 check", "health.datapath_bf16_check", "mi355x_dp_datapath_bf16_checks_total",
+    "bf16 MFMA datapath checks run (128-bit operands, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_bf16_check_failures_total", "bf16 MFMA datapath checks that did not pass"};
 
 void Engine::liveness_pass(Reasons* reasons) {
   std::map<std::string, int> ords = judged_ordinals(*reasons);
@@ -545,7 +549,8 @@ void Engine::liveness_pass(Reasons* reasons) {
   // the same idle GPUs, under the same rule: `idle` is empty while busy state is unknown
   const std::pair<int, std::pair<const DatapathKind*, DatapathState*>> datapath_checks[] = {
       {cfg_.datapath_check_every, {&kDatapathF32, &datapath_}},
-      {cfg_.datapath_i8_check_every, {&kDatapathI8, &datapath_i8_}}};
+      {cfg_.datapath_i8_check_every, {&kDatapathI8, &datapath_i8_}},
+      {cfg_.datapath_bf16_check_every, {&kDatapathBf16, &datapath_bf16_}}};
   for (const auto& [every, check] : datapath_checks) {
     if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
@@ -554,7 +559,7 @@ void Engine::liveness_pass(Reasons* reasons) {
     if (!cand.empty()) datapath_check(cand, *check.first, check.second);
   }
   std::lock_guard<std::mutex> lk(mu_);
-  for (const DatapathState* st : {&datapath_, &datapath_i8_})
+  for (const DatapathState* st : {&datapath_, &datapath_i8_, &datapath_bf16_})
     for (const auto& [id, why] : st->failed)
       if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
@@ -1037,6 +1042,11 @@ std::map<std::string, std::string> Engine::datapath_failed() const {
 std::map<std::string, std::string> Engine::datapath_i8_failed() const {
   std::lock_guard<std::mutex> lk(mu_);
   return datapath_i8_.failed;
+}
+
+std::map<std::string, std::string> Engine::datapath_bf16_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_bf16_.failed;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

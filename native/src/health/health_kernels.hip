@@ -4,3 +4,4 @@
 #include "liveness_kernel.hip"
 #include "datapath_kernel.hip"
 #include "datapath_i8_kernel.hip"
+#include "datapath_bf16_kernel.hip"

@@ -1,5 +1,5 @@
 // The JSON the probe prints: a device's object for the liveness probe, a chip
-// sweep, a throughput check and the two datapath checks, the server's hello,
+// sweep, a throughput check and the three datapath checks, the server's hello,
 // and the lines around the devices, --serve and one-shot (shared by
 // probe_main.cpp and the contract CLIs under native/tests, so a test sees
 // exactly the line the prober parses), and the blank result each check starts
@@ -137,6 +137,9 @@ inline std::string datapath_i8_json(const mi355x_datapath_i8_result& r) {
       json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
 }
 
+// the bf16 check's result is the int8 check's (liveness_probe.h): the same line
+inline std::string datapath_bf16_json(const mi355x_datapath_bf16_result& r) { return datapath_i8_json(r); }
+
 // phase_us of one device: HSA build = code object, queue, buffers, dispatch;
 // HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch
 inline std::string device_json(const mi355x_probe_result& r, bool hsa_build) {
@@ -184,7 +187,9 @@ inline std::string serve_reply_json(bool tagged, unsigned long long id, const st
       "{%s\"ok\":%s,\"hip_device_count\":%d,\"sweep\":%s,\"perf\":%s,\"t_ready_ns\":%llu,", id_field(tagged, id).c_str(),
       ok ? "true" : "false", n, kind == "sweep" ? "true" : "false", kind == "perf" ? "true" : "false",
       static_cast<unsigned long long>(t_ready_ns));
-  const char* key = kind == "datapath" ? "\"datapath\":true," : kind == "datapath_i8" ? "\"datapath_i8\":true," : "";
+  const char* key = kind == "datapath" ? "\"datapath\":true," : kind == "datapath_i8"   ? "\"datapath_i8\":true,"
+                    : kind == "datapath_bf16" ? "\"datapath_bf16\":true,"
+                                              : "";
   return head + key + "\"devices\":" + devices + "}";
 }
 
@@ -202,7 +207,7 @@ inline std::string runtime_init_failed_json(int code, uint64_t t_start_ns, const
       code, static_cast<unsigned long long>(t_start_ns), init_profile.c_str());
 }
 
-// --sweep / --perf / --datapath / --datapath-i8
+// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16
 inline std::string oneshot_check_json(const std::string& kind, bool ok, int n, uint64_t t_start_ns,
                                       uint64_t t_runtime_ns, uint64_t t_ready_ns, const std::string& devices) {
   return json_format(

@@ -6,6 +6,7 @@
 //     [@<id> ]perf <mfma_iters> <timeout_s> <mib> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_bf16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // A device's own deadline (> 0) replaces the request's timeout for that device.
 #pragma once
 
@@ -21,7 +22,7 @@ namespace mi355x {
 struct ServeRequest {
   bool tagged = false;
   unsigned long long id = 0;
-  std::string kind;  // probe | sweep | perf | datapath | datapath_i8
+  std::string kind;  // probe | sweep | perf | datapath | datapath_i8 | datapath_bf16
   int iters = 0;
   double timeout_s = 0;
   unsigned long long perf_mib = 0;
@@ -58,6 +59,9 @@ inline bool parse_request(const std::string& line, ServeRequest* r) {
   } else if (std::strncmp(p, "datapath_i8 ", 12) == 0) {
     r->kind = "datapath_i8";
     parsed = std::sscanf(p, "datapath_i8 %lf %n", &r->timeout_s, &consumed) >= 1;
+  } else if (std::strncmp(p, "datapath_bf16 ", 14) == 0) {
+    r->kind = "datapath_bf16";
+    parsed = std::sscanf(p, "datapath_bf16 %lf %n", &r->timeout_s, &consumed) >= 1;
   } else if (std::strncmp(p, "datapath ", 9) == 0) {
     r->kind = "datapath";
     parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;

@@ -63,9 +63,9 @@ def probe_contract_cli(build_dir: Path) -> Path:
     return compile_cli(Path(build_dir) / "probe_contract_cli", source=PROBE_SOURCE)
 
 
-def probe_replies_text(cli) -> str:
-    """The document `probe_contract_cli replies` prints, as its bytes."""
-    r = subprocess.run([str(cli), "replies"], capture_output=True, text=True, timeout=60)
+def probe_replies_text(cli, command: str = "replies") -> str:
+    """The document `probe_contract_cli replies` (or `replies-bf16`) prints, as its bytes."""
+    r = subprocess.run([str(cli), command], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     return r.stdout
 

@@ -3,7 +3,7 @@ GPU would have left behind, and the shipped host verdict on them.
 
 The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
-(chip_verify.h, datapath_verify.h, datapath_i8_verify.h) says the same of the
+(chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -17,6 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import contract_cli
+from . import datapath_bf16_reference as dpbf
 from . import datapath_i8_reference as dpi8
 from . import datapath_reference as dp
 from . import kernel_reference as ref
@@ -42,8 +43,10 @@ PERF_KEYS = ("ok", "bytes", "num_xcc", "hbm_bad_words", "hbm_bad_words_pass2", "
 DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad", "first_bad_wg", "first_bad_stage",
                  "first_bad_word", "first_bad_got", "first_bad_want", "first_bad_xor", "cus_covered", "simds_covered",
                  "xccs_covered", "error")
-KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS}
-MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES}
+KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
+        "datapath_bf16": DATAPATH_KEYS}
+MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
+         "datapath_bf16": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -113,6 +116,10 @@ def datapath_i8_case(mode: str) -> bytes:
     return _datapath_case(dpi8, mode, 4)
 
 
+def datapath_bf16_case(mode: str) -> bytes:
+    return _datapath_case(dpbf, mode, 4)
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -122,6 +129,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = contract_cli.perf_verdicts(contract_cli.contract_cli(build_dir), [perf_case(m) for m in modes], len(modes))
     elif kind == "datapath":
         out = dp.verdicts(dp.contract_cli(build_dir), [datapath_case(m) for m in modes], len(modes))
+    elif kind == "datapath_bf16":
+        out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:
         out = dpi8.verdicts(dpi8.contract_cli(build_dir), [datapath_i8_case(m) for m in modes], len(modes))
     return dict(zip(modes, out))

@@ -33,6 +33,8 @@ one appends "datapath:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
 int8 MFMA datapath-check replies ("datapath_i8" requests / --datapath-i8)
 follow the "datapath_i8" map with the same modes; each one appends
 "datapath_i8:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
+bf16 MFMA datapath-check replies ("datapath_bf16" requests / --datapath-bf16)
+follow the "datapath_bf16" map, likewise, and append "datapath_bf16:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -87,9 +89,12 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
             "error": "" if ok or mode == "stale" else "17/1024 MFMA results differ from host reference"}
 
 
+DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16")
+
+
 def _log_check(kind, host_ordinal):
     log = os.environ.get("MI355X_STUB_PROBE_LOG")
-    if log and kind in ("datapath", "datapath_i8"):
+    if log and kind in DATAPATH_KINDS:
         with open(log, "a") as f:
             f.write(f"{kind}:{host_ordinal}\n")
 
@@ -153,8 +158,9 @@ def _perf_device(ordinal_reported, mode, nonce, host_ordinal=None):
                      if bad else ""}
 
 
-def _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, stages, stuck, kernel_us, total_us):
-    who = _identity(ordinal_reported if host_ordinal is None else host_ordinal, "datapath" if stages == 4 else "datapath_i8")
+def _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, stages, stuck, kernel_us, total_us, kind=None):
+    who = _identity(ordinal_reported if host_ordinal is None else host_ordinal,
+                    kind or ("datapath" if stages == 4 else "datapath_i8"))
     d = {"ordinal": ordinal_reported, "ok": mode == "ok", "hsa_error": 0, "nonce": nonce, "grid": 256, "cu_count": 256,
          "num_xcc": 8, "records_ok": 256, "mfma_bad": 0, "stage_bad": [0] * stages, "tile_bad": 0,
          "first_bad_wg": -1, "first_bad_stage": -1, "first_bad_word": -1, "first_bad_got": 0, "first_bad_want": 0,
@@ -196,8 +202,19 @@ def _datapath_i8_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 5, stuck, 25.0, 2000.0)
 
 
+def _datapath_bf16_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """bf16 MFMA datapath-check reply (kind "datapath_bf16"); the modes of
+    _datapath_device, from the control file's "datapath_bf16" map (stuck_bit: bit
+    30 of every stage-4 word of one CU's tile)."""
+    stuck = dict(records_ok=255, tile_bad=196, first_bad_wg=17, first_bad_stage=4, first_bad_word=0,
+                 first_bad_got=0x02A8F830, first_bad_want=0x42A8F830, first_bad_xor=0x40000000,
+                 error="255/256 workgroups exact (device_bad=0 tile_bad=196); first bad: wg 17 stage 4 word 0 "
+                       "xor 0x40000000 (bit 30)")
+    return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 5, stuck, 30.0, 2500.0, kind="datapath_bf16")
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
-                "datapath_i8": _datapath_i8_device}
+                "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -267,7 +284,8 @@ _INT = r"\s*([+-]?\d+)"
 _UINT0 = r"\s*([+-]?(?:0[xX][0-9a-fA-F]+|0[0-7]*|[1-9]\d*))"   # strtoul, base 0
 _FLOAT = r"\s*([+-]?(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?)"   # strtod / %lf, decimal forms
 # like sscanf, field by field: each takes all it can and gives nothing back to the next
-_HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapath", (_FLOAT,)),
+_HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapath_bf16", (_FLOAT,)),
+          ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
 
@@ -326,7 +344,7 @@ def _envelope(kind, ok, count, devices, rid=None):
     """The line around a --serve reply's devices (probe_json.h serve_reply_json)."""
     doc = {"ok": ok, "hip_device_count": count, "sweep": kind == "sweep", "perf": kind == "perf",
            "t_ready_ns": time.monotonic_ns()}
-    if kind in ("datapath", "datapath_i8"):
+    if kind in DATAPATH_KINDS:
         doc[kind] = True
     doc["devices"] = devices
     return doc if rid is None else {"id": rid, **doc}
@@ -379,7 +397,7 @@ def serve():
             d = _blank(kind, o)
             d["error"] = "no such GPU (count=8)"
             return d
-        if kind in ("perf", "datapath", "datapath_i8"):
+        if kind == "perf" or kind in DATAPATH_KINDS:
             mode = ctl.get(kind, {}).get(hosto, "ok")
             if mode == "hang":   # a check that never finishes (the daemon stops meanwhile)
                 time.sleep(3600)
@@ -556,6 +574,7 @@ def main(argv):
     ctl = _control()
     mode = ctl.get(ordinal, "ok")
     for flag, kind in (("--perf", "perf"), ("--datapath", "datapath"), ("--datapath-i8", "datapath_i8"),
+                       ("--datapath-bf16", "datapath_bf16"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
