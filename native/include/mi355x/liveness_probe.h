@@ -320,6 +320,50 @@ int mi355x_hsa_datapath_bf16_check(int ordinal, uint32_t nonce, double timeout_s
 // Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later bf16 check.
 void mi355x_hsa_datapath_bf16_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- fp8 / MX-scaled MFMA datapath check (64- and 256-bit operands, bit-exact) --
+// The same shape once more, on the 8-bit float part of the matrix core: three
+// v_mfma_f32_32x32x16_{fp8,bf8}_{fp8,bf8} stages, one
+// v_mfma_f32_16x16x32_bf8_fp8 stage, three v_mfma_scale_f32_32x32x64_f8f6f4
+// stages and one v_mfma_scale_f32_16x16x128_f8f6f4 stage per wave, on e4m3 /
+// e5m2 operands and E8M0 scales for which every product and every partial sum,
+// in any order, is an exact f32 (datapath_fp8_kernel.h). Each wave checks its
+// accumulators, as words, against a VALU fmaf recomputation; the host checks
+// wave 0's eight tiles of every workgroup word for word. The fields have the
+// int8 check's meanings (mfma_bad counts f32 words); stage_bad has 8 entries.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[8];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;     // row * 32 + column (stages 3 and 7: row * 16 + column)
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double kernel_us;
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_fp8_result;
+
+int mi355x_hsa_datapath_fp8_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_fp8_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later fp8 check (stage 0..7).
+void mi355x_hsa_datapath_fp8_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

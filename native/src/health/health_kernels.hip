@@ -5,3 +5,4 @@
 #include "datapath_kernel.hip"
 #include "datapath_i8_kernel.hip"
 #include "datapath_bf16_kernel.hip"
+#include "datapath_fp8_kernel.hip"

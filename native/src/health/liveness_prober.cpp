@@ -446,6 +446,7 @@ std::map<int, ProbeOutcome> LivenessProber::spawn_all(const std::vector<int>& or
       if (kind == "datapath") argv.push_back("--datapath");
       if (kind == "datapath_i8") argv.push_back("--datapath-i8");
       if (kind == "datapath_bf16") argv.push_back("--datapath-bf16");
+      if (kind == "datapath_fp8") argv.push_back("--datapath-fp8");
       if (kind == "perf")
         for (const std::string& a : {std::string("--perf"), std::string("--perf-mib"), std::to_string(cfg_.perf_mib),
                                      std::string("--perf-iters"), std::to_string(cfg_.perf_iters)})
@@ -674,7 +675,8 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
   char head[96];
   if (kind == "perf")
     std::snprintf(head, sizeof(head), "perf %d %.3f %d", cfg_.perf_iters, top, cfg_.perf_mib);
-  else if (kind == "datapath" || kind == "datapath_i8" || kind == "datapath_bf16")
+  else if (kind == "datapath" || kind == "datapath_i8" || kind == "datapath_bf16" ||
+           kind == "datapath_fp8")
     std::snprintf(head, sizeof(head), "%s %.3f", kind.c_str(), top);
   else
     std::snprintf(head, sizeof(head), "%s %d %.3f", kind.c_str(), cfg_.iters, top);

@@ -8,12 +8,14 @@
 //   mi355x-liveness-probe --datapath [--devices ..] (full-width bit-exact MFMA operands, see mi355x_mfma_datapath)
 //   mi355x-liveness-probe --datapath-i8 [--devices ..] (128-bit int8 operands, see mi355x_mfma_datapath_i8)
 //   mi355x-liveness-probe --datapath-bf16 [--devices ..] (128-bit bf16 operands, see mi355x_mfma_datapath_bf16)
+//   mi355x-liveness-probe --datapath-fp8 [--devices ..] (fp8 / MX-scaled operands, see mi355x_mfma_datapath_fp8)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
 //   --corrupt-datapath S:W:B[@O]: flip bit B of word W of workgroup 0's stage S tile before the datapath verdict
 //   --corrupt-datapath-i8 S:W:B[@O]: the same for the int8 datapath check (S 0..4)
 //   --corrupt-datapath-bf16 S:W:B[@O]: the same for the bf16 datapath check (S 0..4)
+//   --corrupt-datapath-fp8 S:W:B[@O]: the same for the fp8 datapath check (S 0..7)
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -78,6 +80,7 @@ uint64_t mono_ns() {
 
 using mi355x::blank_result;
 using mi355x::datapath_bf16_json;
+using mi355x::datapath_fp8_json;
 using mi355x::datapath_i8_json;
 using mi355x::datapath_json;
 using mi355x::json_escape;
@@ -128,6 +131,12 @@ int datapath_bf16_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath
 void datapath_bf16_corrupt(int stage, int word, int bit, int ordinal) {
   mi355x_hsa_datapath_bf16_corrupt(stage, word, bit, ordinal);
 }
+int datapath_fp8_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_fp8_result* r) {
+  return mi355x_hsa_datapath_fp8_check(o, nonce, timeout_s, r);
+}
+void datapath_fp8_corrupt(int stage, int word, int bit, int ordinal) {
+  mi355x_hsa_datapath_fp8_corrupt(stage, word, bit, ordinal);
+}
 void init_phases(double out[5]) { mi355x_hsa_init_phases(out); }
 void defer_teardown() { mi355x_hsa_probe_defer_release(1); }
 void teardown() { mi355x_hsa_probe_release(); }
@@ -172,6 +181,10 @@ int datapath_i8_check(int o, uint32_t nonce, double, mi355x_datapath_i8_result* 
 void datapath_bf16_corrupt(int, int, int, int) {}
 int datapath_bf16_check(int o, uint32_t nonce, double, mi355x_datapath_bf16_result* r) {
   return needs_hsa_build("--datapath-bf16", blank_result<mi355x_datapath_bf16_result>(o, nonce), r);
+}
+void datapath_fp8_corrupt(int, int, int, int) {}
+int datapath_fp8_check(int o, uint32_t nonce, double, mi355x_datapath_fp8_result* r) {
+  return needs_hsa_build("--datapath-fp8", blank_result<mi355x_datapath_fp8_result>(o, nonce), r);
 }
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
   auto blank = blank_result<mi355x_perf_result>(o, nonce);
@@ -327,7 +340,7 @@ bool run_on_each(const std::vector<int>& ords, const std::vector<uint32_t>& nonc
   return ok;
 }
 
-// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 and the server's requests of those kinds.
+// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 and the server's requests of those kinds.
 // `iters`: the sweep's tile iterations or the throughput check's MFMA
 // iterations; `bytes`: the throughput check's HBM buffer.
 bool run_check(const std::string& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
@@ -348,12 +361,16 @@ bool run_check(const std::string& kind, const std::vector<int>& ords, const std:
     return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_bf16_result* r) {
       return datapath_bf16_check(o, nonce, t, r);
     }, datapath_bf16_json, json);
+  if (kind == "datapath_fp8")
+    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_fp8_result* r) {
+      return datapath_fp8_check(o, nonce, t, r);
+    }, datapath_fp8_json, json);
   return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_result* r) {
     return datapath_check(o, nonce, t, r);
   }, datapath_json, json);
 }
 
-// "S:W:B" or "S:W:B@O" of --corrupt-datapath, --corrupt-datapath-i8 and --corrupt-datapath-bf16
+// "S:W:B" or "S:W:B@O" of --corrupt-datapath, --corrupt-datapath-i8, --corrupt-datapath-bf16 and --corrupt-datapath-fp8
 bool parse_corrupt_datapath(const char* spec, int out[4]) {
   out[3] = -1;
   char tail = 0;
@@ -378,6 +395,7 @@ std::string devices_json(const std::vector<mi355x_probe_result>& results) {
 //     [@<id> ]datapath <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_bf16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_fp8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // is answered with one JSON line {"id":..,"ok":..,"t_ready_ns":..,"devices":[..]}
 // ("id" only for a tagged request). A device's own deadline replaces the
 // request's timeout for that device: the plugin gives GPUs that run other
@@ -534,6 +552,7 @@ int main(int argc, char** argv) {
   bool datapath_mode = false;
   bool datapath_i8_mode = false;
   bool datapath_bf16_mode = false;
+  bool datapath_fp8_mode = false;
   uint64_t perf_mib = 4096;
   int perf_iters = 1 << 16;
   uint64_t peer_bytes = 64ull << 20;
@@ -602,6 +621,15 @@ int main(int argc, char** argv) {
         return 2;
       }
       datapath_bf16_corrupt(c[0], c[1], c[2], c[3]);
+    } else if (a == "--datapath-fp8") {
+      datapath_fp8_mode = true;
+    } else if (a == "--corrupt-datapath-fp8") {
+      int c[4];
+      if (!parse_corrupt_datapath(next("--corrupt-datapath-fp8"), c)) {
+        std::fprintf(stderr, "--corrupt-datapath-fp8 must be STAGE:WORD:BIT[@ORDINAL]\n");
+        return 2;
+      }
+      datapath_fp8_corrupt(c[0], c[1], c[2], c[3]);
     } else if (a == "--perf-mib") {
       perf_mib = std::strtoull(next("--perf-mib"), nullptr, 0);
     } else if (a == "--perf-iters") {
@@ -627,6 +655,7 @@ int main(int argc, char** argv) {
                   "[--perf [--perf-mib M] [--perf-iters N] [--poison-hbm UNIT]] [--datapath [--corrupt-datapath S:W:B[@ORDINAL]]] "
                   "[--datapath-i8 [--corrupt-datapath-i8 S:W:B[@ORDINAL]]] "
                   "[--datapath-bf16 [--corrupt-datapath-bf16 S:W:B[@ORDINAL]]] "
+                  "[--datapath-fp8 [--corrupt-datapath-fp8 S:W:B[@ORDINAL]]] "
                   "[--corrupt-word K[@ORDINAL]] [--hip-stream own|null]\n",
                   argv[0]);
       return 0;
@@ -675,9 +704,10 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> nonces;
   for (size_t i = 0; i < ords.size(); ++i) nonces.push_back(nonce + static_cast<uint32_t>(i));
   const std::vector<double> timeouts(ords.size(), timeout_s);
-  if (perf_mode || datapath_mode || datapath_i8_mode || datapath_bf16_mode || sweep_mode) {
+  if (perf_mode || datapath_mode || datapath_i8_mode || datapath_bf16_mode || datapath_fp8_mode ||
+      sweep_mode) {
     const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : datapath_i8_mode ? "datapath_i8"
-                       : datapath_bf16_mode ? "datapath_bf16" : "sweep";
+                       : datapath_bf16_mode ? "datapath_bf16" : datapath_fp8_mode ? "datapath_fp8" : "sweep";
     std::string body;
     const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
     std::printf("%s\n", mi355x::oneshot_check_json(kind, ok, n, t_start, t_runtime, mono_ns(), body).c_str());

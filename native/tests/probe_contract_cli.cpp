@@ -14,6 +14,7 @@
 //        "bad_request": "untagged" and "tagged"; "runtime_init_failed"
 //   probe_contract_cli replies-bf16   the "devices", "serve" and "oneshot" entries of the datapath_bf16 kind, in
 //        a document of its own (tests/test_probe_contract_bf16.py): `replies` stays as recorded
+//   probe_contract_cli replies-fp8    the same for the datapath_fp8 kind (tests/test_probe_contract_fp8.py)
 //   probe_contract_cli parse < lines  per request line one JSON line: the parsed request
 //        {"tagged","id","kind","iters","timeout","mib","devices":[[ordinal,nonce,deadline],..]},
 //        or "bad request" for a line the server refuses
@@ -221,6 +222,20 @@ int cmd_replies_bf16() {
   return 0;
 }
 
+int cmd_replies_fp8() {
+  const uint64_t t0 = 1000000001ull, t1 = 1000000002ull, t2 = 1000000003ull;
+  const char* kind = "datapath_fp8";
+  std::string o = "{\n\"devices\":{\n\"datapath_fp8\":" +
+                  three(datapath_fp8_json(blank_result<mi355x_datapath_fp8_result>(0, 0)),
+                        datapath_fp8_json(filled_datapath<mi355x_datapath_fp8_result>(8)),
+                        datapath_fp8_json(filled_datapath<mi355x_datapath_fp8_result>(16)));
+  o += "},\n\"serve\":{\n\"datapath_fp8\":{\"untagged\":" + serve_reply_json(false, 0, kind, true, 8, t2, "[]") +
+       ",\n\"tagged\":" + serve_reply_json(true, 5, kind, false, 8, t2, "[]") + "}";
+  o += "},\n\"oneshot\":{\n\"datapath_fp8\":" + oneshot_check_json(kind, true, 8, t0, t1, t2, "[]") + "}\n}\n";
+  std::fputs(o.c_str(), stdout);
+  return 0;
+}
+
 int cmd_parse() {
   char buf[8192];  // the server's own line buffer
   while (std::fgets(buf, sizeof(buf), stdin)) {
@@ -246,7 +261,8 @@ int main(int argc, char** argv) {
   const std::string cmd = argc > 1 ? argv[1] : "";
   if (cmd == "replies") return cmd_replies();
   if (cmd == "replies-bf16") return cmd_replies_bf16();
+  if (cmd == "replies-fp8") return cmd_replies_fp8();
   if (cmd == "parse") return cmd_parse();
-  std::fprintf(stderr, "usage: %s replies|replies-bf16|parse\n", argv[0]);
+  std::fprintf(stderr, "usage: %s replies|replies-bf16|replies-fp8|parse\n", argv[0]);
   return 2;
 }

@@ -35,6 +35,8 @@ follow the "datapath_i8" map with the same modes; each one appends
 "datapath_i8:<host ordinal>" to $MI355X_STUB_PROBE_LOG.
 bf16 MFMA datapath-check replies ("datapath_bf16" requests / --datapath-bf16)
 follow the "datapath_bf16" map, likewise, and append "datapath_bf16:<host ordinal>".
+fp8 / MX-scaled MFMA datapath-check replies ("datapath_fp8" requests /
+--datapath-fp8) follow the "datapath_fp8" map and append "datapath_fp8:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -89,7 +91,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
             "error": "" if ok or mode == "stale" else "17/1024 MFMA results differ from host reference"}
 
 
-DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16")
+DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8")
 
 
 def _log_check(kind, host_ordinal):
@@ -213,8 +215,20 @@ def _datapath_bf16_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 5, stuck, 30.0, 2500.0, kind="datapath_bf16")
 
 
+def _datapath_fp8_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """fp8 / MX-scaled MFMA datapath-check reply (kind "datapath_fp8"; eight
+    stages); the modes of _datapath_device, from the control file's
+    "datapath_fp8" map (stuck_bit: bit 30 of every stage-4 word of one CU's tile)."""
+    stuck = dict(records_ok=255, tile_bad=473, first_bad_wg=17, first_bad_stage=4, first_bad_word=0,
+                 first_bad_got=0x98800000, first_bad_want=0xD8800000, first_bad_xor=0x40000000,
+                 error="255/256 workgroups exact (device_bad=0 tile_bad=473); first bad: wg 17 stage 4 word 0 "
+                       "xor 0x40000000 (bit 30)")
+    return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 8, stuck, 60.0, 3000.0, kind="datapath_fp8")
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
-                "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device}
+                "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
+                "datapath_fp8": _datapath_fp8_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -285,6 +299,7 @@ _UINT0 = r"\s*([+-]?(?:0[xX][0-9a-fA-F]+|0[0-7]*|[1-9]\d*))"   # strtoul, base 0
 _FLOAT = r"\s*([+-]?(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?)"   # strtod / %lf, decimal forms
 # like sscanf, field by field: each takes all it can and gives nothing back to the next
 _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapath_bf16", (_FLOAT,)),
+          ("datapath_fp8", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -574,7 +589,7 @@ def main(argv):
     ctl = _control()
     mode = ctl.get(ordinal, "ok")
     for flag, kind in (("--perf", "perf"), ("--datapath", "datapath"), ("--datapath-i8", "datapath_i8"),
-                       ("--datapath-bf16", "datapath_bf16"),
+                       ("--datapath-bf16", "datapath_bf16"), ("--datapath-fp8", "datapath_fp8"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
