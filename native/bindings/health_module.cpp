@@ -58,6 +58,7 @@ class PyHealthEngine {
     i("datapath_i8_check_every", &c.datapath_i8_check_every);
     i("datapath_bf16_check_every", &c.datapath_bf16_check_every);
     i("datapath_fp8_check_every", &c.datapath_fp8_check_every);
+    i("datapath_f16_check_every", &c.datapath_f16_check_every);
     d("perf_min_hbm_read_gbps", &c.perf_min_hbm_read_gbps);
     d("perf_min_hbm_write_gbps", &c.perf_min_hbm_write_gbps);
     d("perf_min_mfma_tflops", &c.perf_min_mfma_tflops);
@@ -118,6 +119,8 @@ class PyHealthEngine {
     d["datapath_bf16_failures"] = eng_->datapath_bf16_failures();
     d["datapath_fp8_checks"] = eng_->datapath_fp8_checks();
     d["datapath_fp8_failures"] = eng_->datapath_fp8_failures();
+    d["datapath_f16_checks"] = eng_->datapath_f16_checks();
+    d["datapath_f16_failures"] = eng_->datapath_f16_failures();
     if (auto* p = eng_->prober()) {
       d["server_starts"] = p->server_starts.load();
       d["server_restarts"] = p->server_restarts.load();

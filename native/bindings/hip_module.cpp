@@ -47,8 +47,8 @@ py::dict to_dict(const mi355x_probe_result& r) {
 
 }  // namespace
 
-// mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result (the same fields; stage_bad
-// differs in length)
+// mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result / _f16_result (the same
+// fields; stage_bad differs in length)
 template <typename R>
 py::dict datapath_dict(const R& r) {
   py::dict d;
@@ -204,6 +204,17 @@ PYBIND11_MODULE(_hip, m) {
         {
           py::gil_scoped_release nogil;
           mi355x_hsa_datapath_fp8_check(ordinal, nonce, timeout_s, &r);
+        }
+        return datapath_dict(r);
+      },
+      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+  m.def(
+      "hsa_datapath_f16_check",
+      [](int ordinal, uint32_t nonce, double timeout_s) {
+        mi355x_datapath_f16_result r;
+        {
+          py::gil_scoped_release nogil;
+          mi355x_hsa_datapath_f16_check(ordinal, nonce, timeout_s, &r);
         }
         return datapath_dict(r);
       },

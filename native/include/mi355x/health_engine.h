@@ -209,6 +209,8 @@ struct Config {
   int datapath_bf16_check_every = 0;
   // and for the fp8 / MX-scaled MFMA datapath check, likewise (0 = off)
   int datapath_fp8_check_every = 0;
+  // and for the f16 MFMA datapath check, likewise (0 = off)
+  int datapath_f16_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_hbm_write_gbps = 2000.0;
   double perf_min_mfma_tflops = 700.0;
@@ -283,6 +285,10 @@ class Engine {
   uint64_t datapath_fp8_failures() const { return datapath_fp8_.failures; }
   // and for the fp8 / MX-scaled MFMA datapath check
   std::map<std::string, std::string> datapath_fp8_failed() const;
+  uint64_t datapath_f16_checks() const { return datapath_f16_.checks; }
+  uint64_t datapath_f16_failures() const { return datapath_f16_.failures; }
+  // and for the f16 MFMA datapath check
+  std::map<std::string, std::string> datapath_f16_failed() const;
   // device -> (ok | degraded | failed, reason) of its last throughput check
   std::map<std::string, std::pair<std::string, std::string>> perf_verdicts() const;
   std::map<std::string, ProbeOutcome> perf_last() const;  // device -> its last throughput-check reply
@@ -335,8 +341,8 @@ class Engine {
     uint64_t checks = 0, failures = 0;
     std::map<std::string, std::string> failed;  // guarded by mu_
   };
-  struct DatapathKind;  // the f32, the int8, the bf16 or the fp8 check: request verb, wording, series names
-  static const DatapathKind kDatapathF32, kDatapathI8, kDatapathBf16, kDatapathFp8;
+  struct DatapathKind;  // the f32, int8, bf16, fp8 or f16 check: request verb, wording, series names
+  static const DatapathKind kDatapathF32, kDatapathI8, kDatapathBf16, kDatapathFp8, kDatapathF16;
   void datapath_check(const std::map<std::string, int>& ords, const DatapathKind& kind, DatapathState* st);
   SmiXgmiSnapshot read_xgmi();
 
@@ -358,7 +364,8 @@ class Engine {
   uint64_t sweeps_ = 0, identity_remaps_ = 0, crowded_skips_ = 0, chip_sweeps_ = 0, perf_checks_ = 0;
   std::map<std::string, std::pair<std::string, std::string>> perf_;  // guarded by mu_
   std::map<std::string, ProbeOutcome> perf_last_;                     // guarded by mu_
-  DatapathState datapath_, datapath_i8_, datapath_bf16_, datapath_fp8_;  // each check keeps failures of its own
+  // each check keeps failures of its own
+  DatapathState datapath_, datapath_i8_, datapath_bf16_, datapath_fp8_, datapath_f16_;
   uint64_t xgmi_readings_ = 0;
   double last_sweep_ms_ = 0;
   int abort_fd_ = -1;

@@ -364,6 +364,50 @@ int mi355x_hsa_datapath_fp8_check(int ordinal, uint32_t nonce, double timeout_s,
 // Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later fp8 check (stage 0..7).
 void mi355x_hsa_datapath_fp8_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- f16 MFMA datapath check (128- and 64-bit operands, bit-exact) -------------
+// The same shape for IEEE half operands: three one-hot stages, one sum stage of
+// v_mfma_f32_32x32x16_f16, and one sum stage each of v_mfma_f32_16x16x32_f16
+// and the legacy 64-bit-operand forms v_mfma_f32_32x32x8_f16 and
+// v_mfma_f32_16x16x16_f16 per wave, on operands for which every product and
+// every partial sum, in any order, is an exact f32 (datapath_f16_kernel.h).
+// Each wave checks its accumulators, as words, against a VALU fmaf
+// recomputation; the host checks wave 0's seven tiles of every workgroup word
+// for word. The fields have the int8 check's meanings (mfma_bad counts f32
+// words); stage_bad has 7 entries.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[7];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;     // row * 32 + column (stages 4 and 6: row * 16 + column)
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double kernel_us;
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_f16_result;
+
+int mi355x_hsa_datapath_f16_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_f16_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later f16 check (stage 0..6).
+void mi355x_hsa_datapath_f16_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

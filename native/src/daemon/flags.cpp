@@ -20,7 +20,7 @@ std::string usage(const std::string& argv0) {
          "[-liveness_fail_threshold N] [-liveness_busy_grace S] [-liveness_unknown_busy_grace S] "
          "[-liveness_corroborate] [-liveness_crowded_procs N] [-liveness_probe PATH] [-liveness_chip_sweep_every N] "
          "[-perf_check_every N [-perf_mib N] [-perf_action report|unhealthy] [-perf_min_hbm_read_gbps X] "
-         "[-perf_min_mfma_tflops X] [-perf_min_xcd_clock_ratio X]] [-datapath_check_every N] [-datapath_i8_check_every N] [-datapath_bf16_check_every N] [-datapath_fp8_check_every N]] [-smi_ecc] [-smi_events] [-smi_xgmi] "
+         "[-perf_min_mfma_tflops X] [-perf_min_xcd_clock_ratio X]] [-datapath_check_every N] [-datapath_i8_check_every N] [-datapath_bf16_check_every N] [-datapath_fp8_check_every N] [-datapath_f16_check_every N]] [-smi_ecc] [-smi_events] [-smi_xgmi] "
          "[-dry_run] [-trace_file PATH] [-node_view [-node_view_alias PATH]] [-topology_view] [-device_ids ID,...] "
          "[-log_format glog|json] [-v N] [-logtostderr] [-alsologtostderr] [-stderrthreshold SEV] [-log_dir DIR] "
          "[-vmodule P=N] [-log_backtrace_at FILE:N]\n";
@@ -49,7 +49,8 @@ bool parse_flags(int argc, char** argv, Flags* f, std::string* err, bool* help, 
       {"perf_mib", &f->perf_mib}, {"datapath_check_every", &f->datapath_check_every},
       {"datapath_i8_check_every", &f->datapath_i8_check_every},
       {"datapath_bf16_check_every", &f->datapath_bf16_check_every},
-      {"datapath_fp8_check_every", &f->datapath_fp8_check_every}};
+      {"datapath_fp8_check_every", &f->datapath_fp8_check_every},
+      {"datapath_f16_check_every", &f->datapath_f16_check_every}};
   std::map<std::string, double*> floats = {
       {"liveness_timeout", &f->liveness_timeout}, {"liveness_busy_grace", &f->liveness_busy_grace},
       {"prestart_budget", &f->prestart_budget}, {"liveness_busy_deadline", &f->liveness_busy_deadline},
@@ -159,6 +160,8 @@ bool parse_flags(int argc, char** argv, Flags* f, std::string* err, bool* help, 
     return *err = "datapath_bf16_check_every needs -liveness (the datapath check runs in the probe server)", false;
   if (f->datapath_fp8_check_every > 0 && !f->liveness)
     return *err = "datapath_fp8_check_every needs -liveness (the datapath check runs in the probe server)", false;
+  if (f->datapath_f16_check_every > 0 && !f->liveness)
+    return *err = "datapath_f16_check_every needs -liveness (the datapath check runs in the probe server)", false;
   return true;
 }
 

@@ -62,6 +62,7 @@ struct Flags {
   int datapath_i8_check_every = 0;
   int datapath_bf16_check_every = 0;
   int datapath_fp8_check_every = 0;
+  int datapath_f16_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_mfma_tflops = 700.0;
   double perf_min_xcd_clock_ratio = 0.6;

@@ -49,6 +49,7 @@ health::Config engine_config(const Flags& f) {
   hc.datapath_i8_check_every = f.datapath_i8_check_every;
   hc.datapath_bf16_check_every = f.datapath_bf16_check_every;
   hc.datapath_fp8_check_every = f.datapath_fp8_check_every;
+  hc.datapath_f16_check_every = f.datapath_f16_check_every;
   hc.perf_min_hbm_read_gbps = f.perf_min_hbm_read_gbps;
   hc.perf_min_mfma_tflops = f.perf_min_mfma_tflops;
   hc.perf_min_xcd_clock_ratio = f.perf_min_xcd_clock_ratio;

@@ -515,6 +515,10 @@ const Engine::DatapathKind Engine::kDatapathFp8 = {
     "datapath_fp8", "datapath fp8 check", "health.datapath_fp8_check", "mi355x_dp_datapath_fp8_checks_total",
     "fp8 / MX-scaled MFMA datapath checks run (64- and 256-bit operands, bit-exact, on the idle GPUs)",
     "mi355x_dp_datapath_fp8_check_failures_total", "fp8 / MX-scaled MFMA datapath checks that did not pass"};
+const Engine::DatapathKind Engine::kDatapathF16 = {
+    "datapath_f16", "datapath f16 check", "health.datapath_f16_check", "mi355x_dp_datapath_f16_checks_total",
+    "f16 MFMA datapath checks run (128- and 64-bit operands, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_f16_check_failures_total", "f16 MFMA datapath checks that did not pass"};
 
 void Engine::liveness_pass(Reasons* reasons) {
   std::map<std::string, int> ords = judged_ordinals(*reasons);
@@ -555,7 +559,8 @@ void Engine::liveness_pass(Reasons* reasons) {
       {cfg_.datapath_check_every, {&kDatapathF32, &datapath_}},
       {cfg_.datapath_i8_check_every, {&kDatapathI8, &datapath_i8_}},
       {cfg_.datapath_bf16_check_every, {&kDatapathBf16, &datapath_bf16_}},
-      {cfg_.datapath_fp8_check_every, {&kDatapathFp8, &datapath_fp8_}}};
+      {cfg_.datapath_fp8_check_every, {&kDatapathFp8, &datapath_fp8_}},
+      {cfg_.datapath_f16_check_every, {&kDatapathF16, &datapath_f16_}}};
   for (const auto& [every, check] : datapath_checks) {
     if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
@@ -564,7 +569,7 @@ void Engine::liveness_pass(Reasons* reasons) {
     if (!cand.empty()) datapath_check(cand, *check.first, check.second);
   }
   std::lock_guard<std::mutex> lk(mu_);
-  for (const DatapathState* st : {&datapath_, &datapath_i8_, &datapath_bf16_, &datapath_fp8_})
+  for (const DatapathState* st : {&datapath_, &datapath_i8_, &datapath_bf16_, &datapath_fp8_, &datapath_f16_})
     for (const auto& [id, why] : st->failed)
       if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
@@ -1057,6 +1062,11 @@ std::map<std::string, std::string> Engine::datapath_bf16_failed() const {
 std::map<std::string, std::string> Engine::datapath_fp8_failed() const {
   std::lock_guard<std::mutex> lk(mu_);
   return datapath_fp8_.failed;
+}
+
+std::map<std::string, std::string> Engine::datapath_f16_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_f16_.failed;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

@@ -6,3 +6,4 @@
 #include "datapath_i8_kernel.hip"
 #include "datapath_bf16_kernel.hip"
 #include "datapath_fp8_kernel.hip"
+#include "datapath_f16_kernel.hip"

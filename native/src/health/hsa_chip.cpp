@@ -4,7 +4,8 @@
 // bf16 MFMA rate, per-XCD clocks) and the MFMA datapath check
 // (mi355x_hsa_datapath_check: full-width operands, bit-exact) and its int8
 // and bf16 siblings (mi355x_hsa_datapath_i8_check, mi355x_hsa_datapath_bf16_check:
-// 128-bit operands; mi355x_hsa_datapath_fp8_check: fp8 and MX-scaled operands), all on the
+// 128-bit operands; mi355x_hsa_datapath_fp8_check: fp8 and MX-scaled operands;
+// mi355x_hsa_datapath_f16_check: f16 operands, the legacy 64-bit forms too), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -26,6 +27,7 @@
 
 #include "chip_verify.h"
 #include "datapath_bf16_verify.h"
+#include "datapath_f16_verify.h"
 #include "datapath_fp8_verify.h"
 #include "datapath_i8_verify.h"
 #include "datapath_verify.h"
@@ -417,6 +419,7 @@ int g_dp_corrupt[4] = {-1, 0, 0, -1};  // stage, word, bit, ordinal
 int g_dpi8_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-i8, likewise
 int g_dpbf_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-bf16, likewise
 int g_dpf8_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-fp8, likewise
+int g_dphf_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f16, likewise
 
 }  // namespace
 }  // namespace mi355x::hsa_rt
@@ -695,5 +698,50 @@ extern "C" int mi355x_hsa_datapath_fp8_check(int ordinal, uint32_t nonce, double
       tiles[dpf8_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
   }
   mi355x::datapath_fp8_verdict(records, tiles, grid, out);
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_f16_corrupt(int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  g_dphf_corrupt[0] = stage;
+  g_dphf_corrupt[1] = word;
+  g_dphf_corrupt[2] = bit;
+  g_dphf_corrupt[3] = ordinal;
+}
+
+extern "C" int mi355x_hsa_datapath_f16_check(int ordinal, uint32_t nonce, double timeout_s,
+                                           mi355x_datapath_f16_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_f16_result>(ordinal, nonce);
+  Check<mi355x_datapath_f16_result> c(ordinal, timeout_s, out);
+  KernelInfo k;
+  // no device memory: records, tiles and kernargs all live in host pools
+  if (!c.begin(false, &mi355x_datapath_f16_result::grid, 1, "datapath_f16",
+               {{"mi355x_mfma_datapath_f16.kd", sizeof(mi355x_datapath_f16_args)}}, &k))
+    return 1;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPHF_REC_WORDS * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPHF_WG_WORDS * sizeof(uint32_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_f16_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  if (!c.run(k, kargs, grid, MI355X_DPHF_THREADS, "datapath f16 check", &out->kernel_us)) return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = g_dphf_corrupt;
+    if (cr[0] >= 0 && cr[0] < MI355X_DPHF_STAGES && cr[1] >= 0 &&
+        cr[1] < static_cast<int>(dphf_dim(cr[0]) * dphf_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      tiles[dphf_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
+  }
+  mi355x::datapath_f16_verdict(records, tiles, grid, out);
   return c.finish();
 }

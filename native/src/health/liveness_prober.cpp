@@ -447,6 +447,7 @@ std::map<int, ProbeOutcome> LivenessProber::spawn_all(const std::vector<int>& or
       if (kind == "datapath_i8") argv.push_back("--datapath-i8");
       if (kind == "datapath_bf16") argv.push_back("--datapath-bf16");
       if (kind == "datapath_fp8") argv.push_back("--datapath-fp8");
+      if (kind == "datapath_f16") argv.push_back("--datapath-f16");
       if (kind == "perf")
         for (const std::string& a : {std::string("--perf"), std::string("--perf-mib"), std::to_string(cfg_.perf_mib),
                                      std::string("--perf-iters"), std::to_string(cfg_.perf_iters)})
@@ -676,7 +677,7 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
   if (kind == "perf")
     std::snprintf(head, sizeof(head), "perf %d %.3f %d", cfg_.perf_iters, top, cfg_.perf_mib);
   else if (kind == "datapath" || kind == "datapath_i8" || kind == "datapath_bf16" ||
-           kind == "datapath_fp8")
+           kind == "datapath_fp8" || kind == "datapath_f16")
     std::snprintf(head, sizeof(head), "%s %.3f", kind.c_str(), top);
   else
     std::snprintf(head, sizeof(head), "%s %d %.3f", kind.c_str(), cfg_.iters, top);

@@ -59,7 +59,7 @@ R blank_result(int ordinal, uint32_t nonce) {
   r.ordinal = ordinal;
   r.nonce = nonce;
   if constexpr (std::is_same_v<R, mi355x_datapath_result> || std::is_same_v<R, mi355x_datapath_i8_result> ||
-                std::is_same_v<R, mi355x_datapath_fp8_result>)
+                std::is_same_v<R, mi355x_datapath_fp8_result> || std::is_same_v<R, mi355x_datapath_f16_result>)
     r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
   if constexpr (!std::is_same_v<R, mi355x_probe_result>) r.kfd_node_id = -1;  // a check that names no agent
   return r;
@@ -158,6 +158,23 @@ inline std::string datapath_fp8_json(const mi355x_datapath_fp8_result& r) {
       json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
 }
 
+// the f16 check's line: the int8 check's with seven stage counts
+inline std::string datapath_f16_json(const mi355x_datapath_f16_result& r) {
+  return json_format(
+      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
+      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u,%u,%u],\"tile_bad\":%u,"
+      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
+      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
+      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
+      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
+      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
+      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.stage_bad[5],
+      r.stage_bad[6], r.tile_bad, r.first_bad_wg, r.first_bad_stage, r.first_bad_word,
+      r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered, r.xccs_covered,
+      r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
+      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
+}
+
 // phase_us of one device: HSA build = code object, queue, buffers, dispatch;
 // HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch
 inline std::string device_json(const mi355x_probe_result& r, bool hsa_build) {
@@ -208,6 +225,7 @@ inline std::string serve_reply_json(bool tagged, unsigned long long id, const st
   const char* key = kind == "datapath" ? "\"datapath\":true," : kind == "datapath_i8"   ? "\"datapath_i8\":true,"
                     : kind == "datapath_bf16" ? "\"datapath_bf16\":true,"
                     : kind == "datapath_fp8"  ? "\"datapath_fp8\":true,"
+                    : kind == "datapath_f16"  ? "\"datapath_f16\":true,"
                                               : "";
   return head + key + "\"devices\":" + devices + "}";
 }
@@ -226,7 +244,7 @@ inline std::string runtime_init_failed_json(int code, uint64_t t_start_ns, const
       code, static_cast<unsigned long long>(t_start_ns), init_profile.c_str());
 }
 
-// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8
+// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16
 inline std::string oneshot_check_json(const std::string& kind, bool ok, int n, uint64_t t_start_ns,
                                       uint64_t t_runtime_ns, uint64_t t_ready_ns, const std::string& devices) {
   return json_format(

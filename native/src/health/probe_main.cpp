@@ -9,6 +9,7 @@
 //   mi355x-liveness-probe --datapath-i8 [--devices ..] (128-bit int8 operands, see mi355x_mfma_datapath_i8)
 //   mi355x-liveness-probe --datapath-bf16 [--devices ..] (128-bit bf16 operands, see mi355x_mfma_datapath_bf16)
 //   mi355x-liveness-probe --datapath-fp8 [--devices ..] (fp8 / MX-scaled operands, see mi355x_mfma_datapath_fp8)
+//   mi355x-liveness-probe --datapath-f16 [--devices ..] (128- and 64-bit f16 operands, see mi355x_mfma_datapath_f16)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
@@ -16,6 +17,7 @@
 //   --corrupt-datapath-i8 S:W:B[@O]: the same for the int8 datapath check (S 0..4)
 //   --corrupt-datapath-bf16 S:W:B[@O]: the same for the bf16 datapath check (S 0..4)
 //   --corrupt-datapath-fp8 S:W:B[@O]: the same for the fp8 datapath check (S 0..7)
+//   --corrupt-datapath-f16 S:W:B[@O]: the same for the f16 datapath check (S 0..6)
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -81,6 +83,7 @@ uint64_t mono_ns() {
 using mi355x::blank_result;
 using mi355x::datapath_bf16_json;
 using mi355x::datapath_fp8_json;
+using mi355x::datapath_f16_json;
 using mi355x::datapath_i8_json;
 using mi355x::datapath_json;
 using mi355x::json_escape;
@@ -137,6 +140,12 @@ int datapath_fp8_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_
 void datapath_fp8_corrupt(int stage, int word, int bit, int ordinal) {
   mi355x_hsa_datapath_fp8_corrupt(stage, word, bit, ordinal);
 }
+int datapath_f16_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_f16_result* r) {
+  return mi355x_hsa_datapath_f16_check(o, nonce, timeout_s, r);
+}
+void datapath_f16_corrupt(int stage, int word, int bit, int ordinal) {
+  mi355x_hsa_datapath_f16_corrupt(stage, word, bit, ordinal);
+}
 void init_phases(double out[5]) { mi355x_hsa_init_phases(out); }
 void defer_teardown() { mi355x_hsa_probe_defer_release(1); }
 void teardown() { mi355x_hsa_probe_release(); }
@@ -185,6 +194,10 @@ int datapath_bf16_check(int o, uint32_t nonce, double, mi355x_datapath_bf16_resu
 void datapath_fp8_corrupt(int, int, int, int) {}
 int datapath_fp8_check(int o, uint32_t nonce, double, mi355x_datapath_fp8_result* r) {
   return needs_hsa_build("--datapath-fp8", blank_result<mi355x_datapath_fp8_result>(o, nonce), r);
+}
+void datapath_f16_corrupt(int, int, int, int) {}
+int datapath_f16_check(int o, uint32_t nonce, double, mi355x_datapath_f16_result* r) {
+  return needs_hsa_build("--datapath-f16", blank_result<mi355x_datapath_f16_result>(o, nonce), r);
 }
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
   auto blank = blank_result<mi355x_perf_result>(o, nonce);
@@ -340,7 +353,8 @@ bool run_on_each(const std::vector<int>& ords, const std::vector<uint32_t>& nonc
   return ok;
 }
 
-// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 and the server's requests of those kinds.
+// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16 and the
+// server's requests of those kinds.
 // `iters`: the sweep's tile iterations or the throughput check's MFMA
 // iterations; `bytes`: the throughput check's HBM buffer.
 bool run_check(const std::string& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
@@ -365,12 +379,16 @@ bool run_check(const std::string& kind, const std::vector<int>& ords, const std:
     return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_fp8_result* r) {
       return datapath_fp8_check(o, nonce, t, r);
     }, datapath_fp8_json, json);
+  if (kind == "datapath_f16")
+    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_f16_result* r) {
+      return datapath_f16_check(o, nonce, t, r);
+    }, datapath_f16_json, json);
   return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_result* r) {
     return datapath_check(o, nonce, t, r);
   }, datapath_json, json);
 }
 
-// "S:W:B" or "S:W:B@O" of --corrupt-datapath, --corrupt-datapath-i8, --corrupt-datapath-bf16 and --corrupt-datapath-fp8
+// "S:W:B" or "S:W:B@O" of --corrupt-datapath and of its -i8, -bf16, -fp8 and -f16 siblings
 bool parse_corrupt_datapath(const char* spec, int out[4]) {
   out[3] = -1;
   char tail = 0;
@@ -396,6 +414,7 @@ std::string devices_json(const std::vector<mi355x_probe_result>& results) {
 //     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_bf16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_fp8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_f16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // is answered with one JSON line {"id":..,"ok":..,"t_ready_ns":..,"devices":[..]}
 // ("id" only for a tagged request). A device's own deadline replaces the
 // request's timeout for that device: the plugin gives GPUs that run other
@@ -553,6 +572,7 @@ int main(int argc, char** argv) {
   bool datapath_i8_mode = false;
   bool datapath_bf16_mode = false;
   bool datapath_fp8_mode = false;
+  bool datapath_f16_mode = false;
   uint64_t perf_mib = 4096;
   int perf_iters = 1 << 16;
   uint64_t peer_bytes = 64ull << 20;
@@ -630,6 +650,15 @@ int main(int argc, char** argv) {
         return 2;
       }
       datapath_fp8_corrupt(c[0], c[1], c[2], c[3]);
+    } else if (a == "--datapath-f16") {
+      datapath_f16_mode = true;
+    } else if (a == "--corrupt-datapath-f16") {
+      int c[4];
+      if (!parse_corrupt_datapath(next("--corrupt-datapath-f16"), c)) {
+        std::fprintf(stderr, "--corrupt-datapath-f16 must be STAGE:WORD:BIT[@ORDINAL]\n");
+        return 2;
+      }
+      datapath_f16_corrupt(c[0], c[1], c[2], c[3]);
     } else if (a == "--perf-mib") {
       perf_mib = std::strtoull(next("--perf-mib"), nullptr, 0);
     } else if (a == "--perf-iters") {
@@ -656,6 +685,7 @@ int main(int argc, char** argv) {
                   "[--datapath-i8 [--corrupt-datapath-i8 S:W:B[@ORDINAL]]] "
                   "[--datapath-bf16 [--corrupt-datapath-bf16 S:W:B[@ORDINAL]]] "
                   "[--datapath-fp8 [--corrupt-datapath-fp8 S:W:B[@ORDINAL]]] "
+                  "[--datapath-f16 [--corrupt-datapath-f16 S:W:B[@ORDINAL]]] "
                   "[--corrupt-word K[@ORDINAL]] [--hip-stream own|null]\n",
                   argv[0]);
       return 0;
@@ -705,9 +735,10 @@ int main(int argc, char** argv) {
   for (size_t i = 0; i < ords.size(); ++i) nonces.push_back(nonce + static_cast<uint32_t>(i));
   const std::vector<double> timeouts(ords.size(), timeout_s);
   if (perf_mode || datapath_mode || datapath_i8_mode || datapath_bf16_mode || datapath_fp8_mode ||
-      sweep_mode) {
+      datapath_f16_mode || sweep_mode) {
     const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : datapath_i8_mode ? "datapath_i8"
-                       : datapath_bf16_mode ? "datapath_bf16" : datapath_fp8_mode ? "datapath_fp8" : "sweep";
+                       : datapath_bf16_mode ? "datapath_bf16" : datapath_fp8_mode ? "datapath_fp8"
+                       : datapath_f16_mode ? "datapath_f16" : "sweep";
     std::string body;
     const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
     std::printf("%s\n", mi355x::oneshot_check_json(kind, ok, n, t_start, t_runtime, mono_ns(), body).c_str());

@@ -8,6 +8,7 @@
 //     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_bf16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_fp8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_f16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // A device's own deadline (> 0) replaces the request's timeout for that device.
 #pragma once
 
@@ -23,7 +24,7 @@ namespace mi355x {
 struct ServeRequest {
   bool tagged = false;
   unsigned long long id = 0;
-  std::string kind;  // probe | sweep | perf | datapath | datapath_i8 | datapath_bf16 | datapath_fp8
+  std::string kind;  // probe | sweep | perf | datapath | datapath_i8 | datapath_bf16 | datapath_fp8 | datapath_f16
   int iters = 0;
   double timeout_s = 0;
   unsigned long long perf_mib = 0;
@@ -66,6 +67,9 @@ inline bool parse_request(const std::string& line, ServeRequest* r) {
   } else if (std::strncmp(p, "datapath_fp8 ", 13) == 0) {
     r->kind = "datapath_fp8";
     parsed = std::sscanf(p, "datapath_fp8 %lf %n", &r->timeout_s, &consumed) >= 1;
+  } else if (std::strncmp(p, "datapath_f16 ", 13) == 0) {
+    r->kind = "datapath_f16";
+    parsed = std::sscanf(p, "datapath_f16 %lf %n", &r->timeout_s, &consumed) >= 1;
   } else if (std::strncmp(p, "datapath ", 9) == 0) {
     r->kind = "datapath";
     parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;

@@ -15,6 +15,7 @@
 //   probe_contract_cli replies-bf16   the "devices", "serve" and "oneshot" entries of the datapath_bf16 kind, in
 //        a document of its own (tests/test_probe_contract_bf16.py): `replies` stays as recorded
 //   probe_contract_cli replies-fp8    the same for the datapath_fp8 kind (tests/test_probe_contract_fp8.py)
+//   probe_contract_cli replies-f16    the same for the datapath_f16 kind (tests/test_probe_contract_f16.py)
 //   probe_contract_cli parse < lines  per request line one JSON line: the parsed request
 //        {"tagged","id","kind","iters","timeout","mib","devices":[[ordinal,nonce,deadline],..]},
 //        or "bad request" for a line the server refuses
@@ -236,6 +237,20 @@ int cmd_replies_fp8() {
   return 0;
 }
 
+int cmd_replies_f16() {
+  const uint64_t t0 = 1000000001ull, t1 = 1000000002ull, t2 = 1000000003ull;
+  const char* kind = "datapath_f16";
+  std::string o = "{\n\"devices\":{\n\"datapath_f16\":" +
+                  three(datapath_f16_json(blank_result<mi355x_datapath_f16_result>(0, 0)),
+                        datapath_f16_json(filled_datapath<mi355x_datapath_f16_result>(8)),
+                        datapath_f16_json(filled_datapath<mi355x_datapath_f16_result>(16)));
+  o += "},\n\"serve\":{\n\"datapath_f16\":{\"untagged\":" + serve_reply_json(false, 0, kind, true, 8, t2, "[]") +
+       ",\n\"tagged\":" + serve_reply_json(true, 5, kind, false, 8, t2, "[]") + "}";
+  o += "},\n\"oneshot\":{\n\"datapath_f16\":" + oneshot_check_json(kind, true, 8, t0, t1, t2, "[]") + "}\n}\n";
+  std::fputs(o.c_str(), stdout);
+  return 0;
+}
+
 int cmd_parse() {
   char buf[8192];  // the server's own line buffer
   while (std::fgets(buf, sizeof(buf), stdin)) {
@@ -262,7 +277,8 @@ int main(int argc, char** argv) {
   if (cmd == "replies") return cmd_replies();
   if (cmd == "replies-bf16") return cmd_replies_bf16();
   if (cmd == "replies-fp8") return cmd_replies_fp8();
+  if (cmd == "replies-f16") return cmd_replies_f16();
   if (cmd == "parse") return cmd_parse();
-  std::fprintf(stderr, "usage: %s replies|replies-bf16|replies-fp8|parse\n", argv[0]);
+  std::fprintf(stderr, "usage: %s replies|replies-bf16|replies-fp8|replies-f16|parse\n", argv[0]);
   return 2;
 }

@@ -15,6 +15,7 @@ Outputs land inside the package so they travel with the repo snapshot:
 * ``bin/datapath_i8_contract_cli`` and for the int8 MFMA datapath check (testing/datapath_i8_reference.py)
 * ``bin/datapath_bf16_contract_cli`` and for the bf16 MFMA datapath check (testing/datapath_bf16_reference.py)
 * ``bin/datapath_fp8_contract_cli`` and for the fp8 / MX-scaled MFMA datapath check (testing/datapath_fp8_reference.py)
+* ``bin/datapath_f16_contract_cli`` and for the f16 MFMA datapath check (testing/datapath_f16_reference.py)
 * ``bin/probe_contract_cli``      host-only driver of the probe's wire format: its reply printers and
   its server's request grammar (testing/contract_cli.py)
 
@@ -48,6 +49,7 @@ DATAPATH_CLI = PKG_DIR / "bin" / "datapath_contract_cli"
 DATAPATH_I8_CLI = PKG_DIR / "bin" / "datapath_i8_contract_cli"
 DATAPATH_BF16_CLI = PKG_DIR / "bin" / "datapath_bf16_contract_cli"
 DATAPATH_FP8_CLI = PKG_DIR / "bin" / "datapath_fp8_contract_cli"
+DATAPATH_F16_CLI = PKG_DIR / "bin" / "datapath_f16_contract_cli"
 PROBE_CONTRACT_CLI = PKG_DIR / "bin" / "probe_contract_cli"
 
 
@@ -221,7 +223,7 @@ def ensure_built(hip: bool | None = None) -> None:
         hip = hipcc_available()
     if hip in _checked:
         return
-    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI, DATAPATH_I8_CLI, DATAPATH_BF16_CLI, DATAPATH_FP8_CLI, PROBE_CONTRACT_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO, HSACO_INJECT] if hip else [])
+    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI, DATAPATH_I8_CLI, DATAPATH_BF16_CLI, DATAPATH_FP8_CLI, DATAPATH_F16_CLI, PROBE_CONTRACT_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO, HSACO_INJECT] if hip else [])
     if not _up_to_date(targets, hip):
         BUILD_DIR.mkdir(parents=True, exist_ok=True)
         with open(BUILD_DIR.parent / ".build.lock", "w") as lk:

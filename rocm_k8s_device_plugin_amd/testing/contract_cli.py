@@ -64,7 +64,8 @@ def probe_contract_cli(build_dir: Path) -> Path:
 
 
 def probe_replies_text(cli, command: str = "replies") -> str:
-    """The document `probe_contract_cli replies` (or `replies-bf16`, `replies-fp8`) prints, as its bytes."""
+    """The document `probe_contract_cli replies` (or `replies-bf16`, `replies-fp8`, `replies-f16`) prints, as
+    its bytes."""
     r = subprocess.run([str(cli), command], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     return r.stdout

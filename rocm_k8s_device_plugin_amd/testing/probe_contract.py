@@ -4,7 +4,7 @@ GPU would have left behind, and the shipped host verdict on them.
 The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
 (chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h,
-datapath_fp8_verify.h) says the same of the
+datapath_fp8_verify.h, datapath_f16_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -20,6 +20,7 @@ import numpy as np
 from . import contract_cli
 from . import datapath_bf16_reference as dpbf
 from . import datapath_fp8_reference as dpf8
+from . import datapath_f16_reference as dphf
 from . import datapath_i8_reference as dpi8
 from . import datapath_reference as dp
 from . import kernel_reference as ref
@@ -46,9 +47,9 @@ DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad"
                  "first_bad_word", "first_bad_got", "first_bad_want", "first_bad_xor", "cus_covered", "simds_covered",
                  "xccs_covered", "error")
 KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
-        "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS}
+        "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS, "datapath_f16": DATAPATH_KEYS}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
-         "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES}
+         "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -139,6 +140,23 @@ def datapath_fp8_case(mode: str, image=None) -> bytes:
     return dpf8.case(recs, tiles, GRID, NONCE)
 
 
+def datapath_f16_case(mode: str, image=None) -> bytes:
+    """As _datapath_case, on stage 4 (the 16x16x32 stage, a tile of 256 words).
+    `image`: the healthy tiles when the caller has them already (the reference takes a while for 256
+    workgroups in Python integers)."""
+    recs, tiles = dphf.healthy(GRID, NONCE, tiles=image)
+    lo = dphf.TILE_OFFSET[4]
+    if mode == "stuck_bit":
+        tiles[WG, lo:lo + dphf.TILE_WORDS[4]] = dphf.stuck_bit(tiles[WG, lo:lo + dphf.TILE_WORDS[4]], BIT, 0)
+    elif mode == "missing":
+        recs[WG:WG + 2, :] = 0
+    elif mode == "device_bad":
+        recs[WG, dphf.REC_BAD + 4] = 12
+    else:
+        assert mode == "ok", mode
+    return dphf.case(recs, tiles, GRID, NONCE)
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -154,6 +172,12 @@ def real_replies(kind: str, build_dir) -> dict:
         image = dpf8.header_tiles(cli, NONCE, GRID)
         assert (image[WG] == dpf8.tiles_image(NONCE ^ (WG * dpf8.GOLDEN & dpf8.M32), 1)[0]).all()
         out = dpf8.verdicts(cli, [datapath_fp8_case(m, image) for m in modes], len(modes))
+    elif kind == "datapath_f16":
+        cli = dphf.contract_cli(build_dir)
+        # the header's own image for the 255 healthy workgroups; the faulty one's tile is the reference's
+        image = dphf.header_tiles(cli, NONCE, GRID)
+        assert (image[WG] == dphf.tiles_image(NONCE ^ (WG * dphf.GOLDEN & dphf.M32), 1)[0]).all()
+        out = dphf.verdicts(cli, [datapath_f16_case(m, image) for m in modes], len(modes))
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:

@@ -16,11 +16,12 @@ REQUESTS.json is a list of requests, run in order:
     {"id": ..., "kernel": "datapath_i8", "nonce": n, "grid": g}
     {"id": ..., "kernel": "datapath_bf16", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
     {"id": ..., "kernel": "datapath_fp8", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
+    {"id": ..., "kernel": "datapath_f16", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
 
-A sweep, datapath, datapath_i8, datapath_bf16 or datapath_fp8 request may add "code_object": "inject": the kernel then comes from
+A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8 or datapath_f16 request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
 the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h /
-datapath_bf16_kernel.h / datapath_fp8_kernel.h), and may add
+datapath_bf16_kernel.h / datapath_fp8_kernel.h / datapath_f16_kernel.h), and may add
 
     "inject": {"kind": "mfma" | "lds", "wg": w, "wave": v, "lane": l, "index": i, "mask": m}
 
@@ -146,6 +147,20 @@ class DatapathFp8InjectArgs(ctypes.Structure):
 DATAPATH_FP8_ARG_STRUCTS = {"mi355x_datapath_fp8_args": DatapathFp8Args}
 DATAPATH_FP8_INJECT_ARG_STRUCTS = {"mi355x_datapath_fp8_args": DatapathFp8InjectArgs}
 DATAPATH_FP8_WG_WORDS = 6 * 32 * 32 + 2 * 16 * 16    # wave 0's eight tiles of one workgroup
+
+
+class DatapathF16Args(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("nonce", _u32), ("grid", _u32)]
+
+
+class DatapathF16InjectArgs(ctypes.Structure):
+    _fields_ = DatapathF16Args._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_f16_kernel.h (native/tests/datapath_f16_contract_cli.cpp prints that header's layouts)
+DATAPATH_F16_ARG_STRUCTS = {"mi355x_datapath_f16_args": DatapathF16Args}
+DATAPATH_F16_INJECT_ARG_STRUCTS = {"mi355x_datapath_f16_args": DatapathF16InjectArgs}
+DATAPATH_F16_WG_WORDS = 5 * 32 * 32 + 2 * 16 * 16    # wave 0's seven tiles of one workgroup
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -156,7 +171,8 @@ def inject_words(req: dict) -> tuple:
     if inj is None:
         return (INJECT_KINDS["none"], 0, 0, 0, 0, 0)
     kind = INJECT_KINDS[inj["kind"]]
-    if req["kernel"] in ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8") and inj["kind"] == "lds":
+    if req["kernel"] in ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
+                         "datapath_f16") and inj["kind"] == "lds":
         raise ValueError("the datapath kernels have no lds injection")
     return (kind, int(inj["wg"]), int(inj.get("wave", 0)), int(inj.get("lane", 0)), int(inj["index"]),
             int(inj["mask"]) & 0xFFFFFFFF)
@@ -166,7 +182,8 @@ def code_object_of(req: dict) -> str:
     which = req.get("code_object", "production")
     if which not in CODE_OBJECTS:
         raise ValueError(f"unknown code object {which!r}")
-    if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8"):
+    if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
+                                                   "datapath_f16"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -179,7 +196,8 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "burn": ("mi355x_mfma_burn", 256), "datapath": ("mi355x_mfma_datapath", 256),
            "datapath_i8": ("mi355x_mfma_datapath_i8", 256),
            "datapath_bf16": ("mi355x_mfma_datapath_bf16", 256),
-           "datapath_fp8": ("mi355x_mfma_datapath_fp8", 256)}
+           "datapath_fp8": ("mi355x_mfma_datapath_fp8", 256),
+           "datapath_f16": ("mi355x_mfma_datapath_f16", 256)}
 
 _H2D, _D2H = 1, 2
 _LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
@@ -327,6 +345,18 @@ def plan(req: dict, base_dir: Path):
         if wgs < g:
             raise ValueError("launch_grid below grid")
         return bufs, lambda p: DatapathFp8Args(p["records"], p["tiles"], req["nonce"], g), wgs
+    if k == "datapath_f16":
+        g = int(req["grid"])
+        bufs = [("records", np.uint32, _filled(g * 16 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * DATAPATH_F16_WG_WORDS * 4, OUT_PREFILL))]
+        if code_object_of(req) == "inject":
+            return bufs, lambda p: DatapathF16InjectArgs(p["records"], p["tiles"], req["nonce"], g,
+                                                         *inject_words(req)), g
+        # the buffers hold `grid` workgroups; the ones launched beyond it must write nothing
+        wgs = int(req.get("launch_grid", g))
+        if wgs < g:
+            raise ValueError("launch_grid below grid")
+        return bufs, lambda p: DatapathF16Args(p["records"], p["tiles"], req["nonce"], g), wgs
     raise ValueError(f"unknown kernel {k!r}")
 
 

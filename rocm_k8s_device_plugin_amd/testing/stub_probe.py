@@ -37,6 +37,8 @@ bf16 MFMA datapath-check replies ("datapath_bf16" requests / --datapath-bf16)
 follow the "datapath_bf16" map, likewise, and append "datapath_bf16:<host ordinal>".
 fp8 / MX-scaled MFMA datapath-check replies ("datapath_fp8" requests /
 --datapath-fp8) follow the "datapath_fp8" map and append "datapath_fp8:<host ordinal>".
+f16 MFMA datapath-check replies ("datapath_f16" requests /
+--datapath-f16) follow the "datapath_f16" map and append "datapath_f16:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -91,7 +93,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
             "error": "" if ok or mode == "stale" else "17/1024 MFMA results differ from host reference"}
 
 
-DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8")
+DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16")
 
 
 def _log_check(kind, host_ordinal):
@@ -226,9 +228,21 @@ def _datapath_fp8_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 8, stuck, 60.0, 3000.0, kind="datapath_fp8")
 
 
+def _datapath_f16_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """f16 MFMA datapath-check reply (kind "datapath_f16"; seven stages); the
+    modes of _datapath_device, from the control file's "datapath_f16" map
+    (stuck_bit: bit 30 of every stage-4 word of one CU's tile)."""
+    stuck = dict(records_ok=255, tile_bad=207, first_bad_wg=17, first_bad_stage=4, first_bad_word=0,
+                 first_bad_got=0x0DE9F070, first_bad_want=0x4DE9F070, first_bad_xor=0x40000000,
+                 error="255/256 workgroups exact (device_bad=0 tile_bad=207); first bad: wg 17 stage 4 word 0 "
+                       "xor 0x40000000 (bit 30)")
+    return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 7, stuck, 35.0, 2600.0, kind="datapath_f16")
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
-                "datapath_fp8": _datapath_fp8_device}
+                "datapath_fp8": _datapath_fp8_device,
+                "datapath_f16": _datapath_f16_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -300,6 +314,7 @@ _FLOAT = r"\s*([+-]?(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?)"   # strtod / %lf, dec
 # like sscanf, field by field: each takes all it can and gives nothing back to the next
 _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapath_bf16", (_FLOAT,)),
           ("datapath_fp8", (_FLOAT,)),
+          ("datapath_f16", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -590,6 +605,7 @@ def main(argv):
     mode = ctl.get(ordinal, "ok")
     for flag, kind in (("--perf", "perf"), ("--datapath", "datapath"), ("--datapath-i8", "datapath_i8"),
                        ("--datapath-bf16", "datapath_bf16"), ("--datapath-fp8", "datapath_fp8"),
+                       ("--datapath-f16", "datapath_f16"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
