@@ -167,6 +167,12 @@ PYBIND11_MODULE(_native, m) {
   m.def("discover_gpus", py::overload_cast<const std::string&>(&discover_gpus), py::arg("sysfs_root") = "/sys");
   m.def("discover_gpus_with", py::overload_cast<const std::string&, const KfdTopology&>(&discover_gpus),
         py::arg("sysfs_root"), py::arg("topology"));
+  m.def("amdgpu_pci_functions", [](const std::string& sysfs_root) {
+    std::vector<std::pair<std::string, std::string>> out;
+    for (auto& fn : amdgpu_pci_functions(sysfs_root)) out.emplace_back(fn.bdf, fn.dir);
+    return out;
+  }, py::arg("sysfs_root") = "/sys");
+  m.def("amdgpu_driver_visible", &amdgpu_driver_visible, py::arg("sysfs_root") = "/sys");
   m.def("partition_config_count", &partition_config_count);
   m.def("is_homogeneous", &is_homogeneous);
   m.def("compute_partition_supported", &compute_partition_supported, py::arg("sysfs_root") = "/sys");

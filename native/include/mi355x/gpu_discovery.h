@@ -5,7 +5,8 @@
 // Behavioural parity with the reference GetAMDGPUs
 // (internal/pkg/amdgpu/amdgpu.go:448-568):
 //   * PCI functions under module/amdgpu/drivers/pci:amdgpu/<BDF> with a readable
-//     numa_node become devices with ID = BDF;
+//     numa_node become devices with ID = BDF (where sysfs has no such driver
+//     directory, see amdgpu_pci_functions);
 //   * amdgpu_xcp_<N> platform devices become devices with ID "amdgpu_xcp_<N>",
 //     inheriting partition modes and NUMA node from their parent (matched by kfd
 //     unique_id) and kept only if their render node is known to kfd.
@@ -63,13 +64,27 @@ struct GpuDevice {
 
 struct DiscoveryResult {
   std::vector<GpuDevice> devices;  // sorted: PCI BDFs first (lexicographic), then xcp by N
-  bool driver_loaded = false;      // <sysfs>/module/amdgpu/drivers exists
+  bool driver_loaded = false;      // amdgpu_driver_visible(<sysfs>)
   bool kfd_present = false;        // <sysfs>/class/kfd exists
   std::vector<std::string> warnings;
   std::vector<int> kfd_unreadable_nodes;  // kfd node dirs whose properties could not be read
   int recovered_devices = 0;              // devices whose identity came from sysfs instead of kfd
   std::vector<std::string> unresolved;    // device IDs with no identity (placement must not trust them)
 };
+
+// The PCI functions amdgpu drives: the entries of
+// module/amdgpu/drivers/pci:amdgpu. A guest may be handed a GPU whose sysfs
+// shows neither that directory nor a driver link on the function (kfd, drm
+// and the function's own attributes are all there); then, and only then, the
+// functions are the AMD ones under bus/pci/devices that carry a drm render
+// node. `dir` is the function's sysfs directory.
+struct AmdgpuFunction {
+  std::string bdf;
+  std::string dir;
+};
+std::vector<AmdgpuFunction> amdgpu_pci_functions(const std::string& sysfs_root);
+// module/amdgpu/drivers exists, or amdgpu_pci_functions finds a function without it
+bool amdgpu_driver_visible(const std::string& sysfs_root);
 
 // Cheap fingerprint of the node's GPU topology: kfd's generation_id (bumped
 // when kfd nodes come or go) and every amdgpu function's current compute /

@@ -331,7 +331,9 @@ bool Engine::update_busy_state(const std::map<std::string, int>& ords, std::set<
   for (const auto& [id, o] : ords) probed_gids.insert(gpu_id(id));
   probed_gids.erase(0);
   const std::set<std::string> own = prober_->own_kfd_entries(probed_gids);
-  const bool unresolved = own.empty() && prober_->server_running() && cfg_.prober.keep_queues;
+  // without a kfd process list there is no entry of the server's to mistake for a tenant's
+  const bool unresolved = own.empty() && prober_->server_running() && cfg_.prober.keep_queues &&
+                          path_exists(path_join(cfg_.sysfs_root, "class/kfd/kfd/proc"));
   const bool known = kfd_load(own, &load_);
   if (!known) {
     load_.clear();
@@ -655,6 +657,23 @@ bool Engine::publish(Reasons reasons) {
   return changed;
 }
 
+namespace {
+// whether a process other than `skip` holds `path` open (/proc/<pid>/fd; a
+// process whose descriptors this one may not read says nothing)
+bool held_by_another_process(const std::string& path, const std::set<std::string>& skip) {
+  for (const auto& pid : list_dir("/proc")) {
+    if (!is_all_digits(pid) || skip.count(pid)) continue;
+    const std::string fds = "/proc/" + pid + "/fd";
+    for (const auto& fd : list_dir(fds)) {
+      char buf[512];
+      const ssize_t n = ::readlink((fds + "/" + fd).c_str(), buf, sizeof(buf) - 1);
+      if (n > 0 && path.compare(0, std::string::npos, buf, static_cast<size_t>(n)) == 0) return true;
+    }
+  }
+  return false;
+}
+}  // namespace
+
 // PreStartContainer's check: beside any sweep, never behind it.
 std::map<std::string, ProbeOutcome> Engine::probe_now(const std::vector<std::string>& ids, double budget_s) {
   if (!cfg_.liveness || !prober_) return {};
@@ -679,9 +698,21 @@ std::map<std::string, ProbeOutcome> Engine::probe_now(const std::vector<std::str
     gids.erase(0);
     std::map<int64_t, std::pair<int, int>> load;
     const bool known = kfd_load(prober_->own_kfd_entries(gids), &load);
+    // a kfd that shows no process list at all (a guest's may not) names no tenant:
+    // there a GPU is another process' when one holds its render node open (this
+    // process, the probe server and Config::kfd_exclude, by PID, are no tenants)
+    const bool listed = path_exists(path_join(cfg_.sysfs_root, "class/kfd/kfd/proc"));
+    std::set<std::string> mine = cfg_.kfd_exclude;
+    mine.insert(std::to_string(::getpid()));
+    mine.insert(std::to_string(prober_->server_pid()));
     std::set<int> busy;
-    for (const auto& [id, o] : sel)
-      if (!known || load.count(gpu_id(id))) busy.insert(o);
+    for (const auto& [id, o] : sel) {
+      const GpuDevice* d = dev(id);
+      const bool held = known && !listed && d && d->render_minor >= 0 &&
+                        held_by_another_process(
+                            path_join(cfg_.dev_root, "dri/renderD" + std::to_string(d->render_minor)), mine);
+      if (!known || load.count(gpu_id(id)) || held) busy.insert(o);
+    }
     return busy;
   };
   const auto by_ord = prober_->check(uniq, busy_of, budget_s);

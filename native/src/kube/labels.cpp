@@ -288,7 +288,7 @@ Labels container_labels(const LabelOptions& f) {
   Ctx c;
   c.sysfs = f.sysfs_root;
   c.dev = f.dev_root;
-  if (is_dir(path_join(f.sysfs_root, "module/amdgpu/drivers"))) {
+  if (amdgpu_driver_visible(f.sysfs_root)) {
     c.topo = KfdTopology::load_sysfs(f.sysfs_root);
     c.gpus = discover_gpus(f.sysfs_root, c.topo).devices;
   }

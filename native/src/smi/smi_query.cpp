@@ -335,7 +335,20 @@ std::string SmiEventWatcher::start(uint64_t mask) {
     bdfs_.push_back(bdf_of(h));
   }
   if (handles_.empty()) {
-    release();
+    // A refused subscription (kfd without SMI events, as in some guests) leaves
+    // the library holding the /dev/kfd descriptor it opened for it, and every
+    // later amdsmi_shut_down closes that descriptor number again, whoever owns it
+    // by then (seen as EBADF in an event loop's epoll). So the first refusal
+    // keeps its reference: the library stays initialised and never shuts down
+    // in this process.
+    static bool kept = false;
+    bool drop = false;
+    {
+      std::lock_guard<std::mutex> lk(g_init_mu);
+      drop = kept;
+      kept = true;
+    }
+    if (drop) release();
     return "no GPU accepted event notification";
   }
   running_ = true;

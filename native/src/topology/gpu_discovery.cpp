@@ -80,7 +80,39 @@ void recover_from_sysfs(GpuDevice* g, const std::string& dev_dir) {
   bdf_location(g->bdf, &g->domain, &g->location_id);
 }
 
+bool has_render_node(const std::string& dev_dir) { return scan_drm(dev_dir).render >= 0; }
+
 }  // namespace
+
+static bool amdgpu_driver_dir_present(const std::string& sysfs_root) {
+  return path_exists(path_join(sysfs_root, "module/amdgpu/drivers"));
+}
+
+std::vector<AmdgpuFunction> amdgpu_pci_functions(const std::string& sysfs_root) {
+  std::vector<AmdgpuFunction> out;
+  if (amdgpu_driver_dir_present(sysfs_root)) {
+    const std::string pci_dir = path_join(sysfs_root, "module/amdgpu/drivers/pci:amdgpu");
+    for (auto& bdf : list_dir(pci_dir))
+      if (looks_like_bdf(bdf)) out.push_back({bdf, path_join(pci_dir, bdf)});
+    return out;
+  }
+  // No driver directory (a guest that is handed the GPU without the module's
+  // sysfs view): an AMD PCI function that carries a drm render node is driven
+  // by amdgpu; functions held by vfio-pci or gim have no drm directory.
+  const std::string pci_dir = path_join(sysfs_root, "bus/pci/devices");
+  for (auto& bdf : list_dir(pci_dir)) {
+    if (!looks_like_bdf(bdf)) continue;
+    const std::string dev_dir = path_join(pci_dir, bdf);
+    auto vendor = read_trimmed(path_join(dev_dir, "vendor"));
+    if (!vendor || parse_i64(*vendor, 0) != 0x1002 || !has_render_node(dev_dir)) continue;
+    out.push_back({bdf, dev_dir});
+  }
+  return out;
+}
+
+bool amdgpu_driver_visible(const std::string& sysfs_root) {
+  return amdgpu_driver_dir_present(sysfs_root) || !amdgpu_pci_functions(sysfs_root).empty();
+}
 
 int partitions_for_mode(const std::string& mode, int total_xcc) {
   if (mode == "spx") return 1;
@@ -107,7 +139,8 @@ DiscoveryResult discover_gpus(const std::string& sysfs_root) {
 DiscoveryResult discover_gpus(const std::string& sysfs_root, const KfdTopology& topo) {
   DiscoveryResult res;
   res.kfd_present = path_exists(path_join(sysfs_root, "class/kfd"));
-  res.driver_loaded = path_exists(path_join(sysfs_root, "module/amdgpu/drivers"));
+  const auto functions = amdgpu_pci_functions(sysfs_root);
+  res.driver_loaded = amdgpu_driver_dir_present(sysfs_root) || !functions.empty();
   res.kfd_unreadable_nodes = topo.unreadable_node_ids();
   if (!res.driver_loaded) {
     res.warnings.push_back("amdgpu driver unavailable: " + path_join(sysfs_root, "module/amdgpu/drivers"));
@@ -116,11 +149,8 @@ DiscoveryResult discover_gpus(const std::string& sysfs_root, const KfdTopology& 
   const auto render_uid = topo.render_to_unique_id();
   const auto render_node = topo.render_to_node_id();
 
-  const std::string pci_dir = path_join(sysfs_root, "module/amdgpu/drivers/pci:amdgpu");
   std::vector<GpuDevice> pci_devs;
-  for (auto& bdf : list_dir(pci_dir)) {
-    if (!looks_like_bdf(bdf)) continue;
-    std::string dev_dir = path_join(pci_dir, bdf);
+  for (auto& [bdf, dev_dir] : functions) {
     GpuDevice g;
     g.id = bdf;
     g.bdf = bdf;
@@ -324,11 +354,7 @@ std::map<std::string, int> partition_config_count(const std::vector<GpuDevice>& 
 bool is_homogeneous(const std::vector<GpuDevice>& devs) { return partition_config_count(devs).size() <= 1; }
 
 static bool first_gpu_has(const std::string& sysfs_root, const char* file) {
-  const std::string pci_dir = path_join(sysfs_root, "module/amdgpu/drivers/pci:amdgpu");
-  for (auto& bdf : list_dir(pci_dir)) {
-    if (!looks_like_bdf(bdf)) continue;
-    return path_exists(path_join(path_join(pci_dir, bdf), file));
-  }
+  for (auto& fn : amdgpu_pci_functions(sysfs_root)) return path_exists(path_join(fn.dir, file));
   return false;
 }
 
@@ -377,13 +403,11 @@ FirmwareInfo parse_debugfs_firmware_info(const std::string& path) {
 
 std::string topology_signature(const std::string& sysfs_root) {
   std::string sig = read_trimmed(path_join(sysfs_root, "class/kfd/kfd/topology/generation_id")).value_or("-");
-  const std::string drv = path_join(sysfs_root, "module/amdgpu/drivers/pci:amdgpu");
-  auto bdfs = list_dir(drv);
-  std::sort(bdfs.begin(), bdfs.end());
-  for (const auto& b : bdfs) {
-    if (b.find(':') == std::string::npos) continue;
-    sig += "|" + b + "=" + read_trimmed(path_join(drv, b + "/current_compute_partition")).value_or("-") + "," +
-           read_trimmed(path_join(drv, b + "/current_memory_partition")).value_or("-");
+  auto fns = amdgpu_pci_functions(sysfs_root);
+  std::sort(fns.begin(), fns.end(), [](const auto& a, const auto& b) { return a.bdf < b.bdf; });
+  for (const auto& fn : fns) {
+    sig += "|" + fn.bdf + "=" + read_trimmed(path_join(fn.dir, "current_compute_partition")).value_or("-") + "," +
+           read_trimmed(path_join(fn.dir, "current_memory_partition")).value_or("-");
   }
   return sig;
 }

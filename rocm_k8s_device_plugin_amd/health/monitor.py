@@ -306,8 +306,9 @@ class HealthMonitor:
         """Devices whose GPU runs other processes' queues (unknown -> all, and
         busy_state_known is cleared so the short grace applies)."""
         own = self._own_entries()
+        # without a kfd process list there is no entry of the server's to mistake for a tenant's
         unresolved = not own and self.prober is not None and self.prober.server_running and \
-            self.prober.keep_queues
+            self.prober.keep_queues and os.path.exists(os.path.join(self.inv.sysfs_root, "class/kfd/kfd/proc"))
         try:
             self._load = kfd_gpu_load(self.inv.sysfs_root, exclude=own)
             busy = set(self._load)

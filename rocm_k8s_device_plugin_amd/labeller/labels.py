@@ -491,8 +491,7 @@ def generate_labels(enabled: Dict[str, bool], driver_type: str = "", sysfs_root:
     def container():
         inv = inventory
         if inv is None:
-            inv = discover(sysfs_root) if os.path.exists(os.path.join(sysfs_root, "module/amdgpu/drivers")) \
-                else None
+            inv = discover(sysfs_root) if core().amdgpu_driver_visible(sysfs_root) else None
         return generate_container_labels(enabled, LabelContext(sysfs_root, dev_root, inv, xgmi_source=xgmi_source))
 
     if driver_type == C.CONTAINER:

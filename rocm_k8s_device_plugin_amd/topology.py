@@ -272,11 +272,7 @@ def topology_signature(sysfs_root: str = "/sys") -> tuple:
         except OSError:
             return None
     gen = rd(os.path.join(sysfs_root, "class/kfd/kfd/topology/generation_id"))
-    drv = os.path.join(sysfs_root, "module/amdgpu/drivers/pci:amdgpu")
-    try:
-        bdfs = sorted(e for e in os.listdir(drv) if ":" in e)
-    except OSError:
-        bdfs = []
-    parts = tuple((b, rd(os.path.join(drv, b, "current_compute_partition")),
-                   rd(os.path.join(drv, b, "current_memory_partition"))) for b in bdfs)
+    parts = tuple((b, rd(os.path.join(d, "current_compute_partition")),
+                   rd(os.path.join(d, "current_memory_partition")))
+                  for b, d in sorted(core().amdgpu_pci_functions(sysfs_root)))
     return gen, parts

@@ -158,14 +158,16 @@ def test_kfd_denied_gpus_identified_from_sysfs(inv, caplog):
             with open(f"{dev_dir}/xgmi_hive_info/xgmi_hive_id") as f:
                 assert int(f.read().strip()) == d.hive_id
     assert all(d.unique_id for d in inv.devices) and inv.placement_trusted
-    if not inv.kfd_unreadable_nodes:
-        pytest.skip("this box's device cgroup hides no GPU")
+    # a node whose every GPU is this process' own (a one-GPU guest) has nothing denied:
+    # then nothing is recovered, and neither the warning nor the log line appears
+    denied = bool(inv.kfd_unreadable_nodes)
     assert sorted(inv.recovered) == sorted(d.id for d in inv.devices if d.identity != "kfd")
-    assert any("unreadable" in w for w in inv.warnings)
+    assert bool(inv.recovered) == denied
+    assert any("unreadable" in w for w in inv.warnings) == denied
     assert len({d.hive_id for d in inv.devices}) == 1      # one 8-GPU xGMI hive
     with caplog.at_level(logging.WARNING):
         impl = ContainerImpl("single", "/sys", HealthConfig(exporter_socket=None), inventory=discover("/sys"))
-    assert any("kfd denies" in r.getMessage() for r in caplog.records)
+    assert any("kfd denies" in r.getMessage() for r in caplog.records) == denied
     assert f"mi355x_dp_kfd_unreadable_nodes {float(len(inv.kfd_unreadable_nodes))}" in REGISTRY.render()
     from rocm_k8s_device_plugin_amd.plugin.base import new_context
     ctx = new_context("gpu")
@@ -622,7 +624,10 @@ def test_persistent_probe_server_keeps_queues(ordinals):
 def test_kept_queue_server_is_not_a_tenant(inv, ordinals):
     """The kept-queue server's own kfd entry is found and excluded: its queue does not make the GPU look busy."""
     from rocm_k8s_device_plugin_amd.health.liveness import LivenessProber
+    from rocm_k8s_device_plugin_amd.testing.kfd_caps import KFD_PROC_DIR, kfd_process_list_present
     from rocm_k8s_device_plugin_amd.topology import kfd_busy_gpu_ids
+    if not kfd_process_list_present():
+        pytest.skip(f"this node's kfd has no process list ({KFD_PROC_DIR}): no entry to find or exclude")
     dev_id, o = sorted(ordinals.items(), key=lambda kv: kv[1])[0]
     gid = inv.topology.node(inv.by_id[dev_id].node_id).gpu_id
     prober = LivenessProber(timeout_s=60, mode="persistent", keep_queues=True)
@@ -688,6 +693,11 @@ def test_smi_event_watcher_subscribes(inv):
     A liveness probe run while subscribed makes kfd emit nothing we subscribe
     to (no reset/fault), so the expectation is an empty or benign list."""
     from rocm_k8s_device_plugin_amd.ops.native import core
+    from rocm_k8s_device_plugin_amd.testing.kfd_caps import kfd_smi_events_refused
+    readable = [d for d in inv.devices if d.identity == "kfd"]
+    refused = kfd_smi_events_refused(inv.topology.node(readable[0].node_id).gpu_id) if readable else ""
+    if refused:
+        pytest.skip(f"this node's kfd hands out no SMI event descriptor ({refused})")
     w = core().SmiEventWatcher()
     mask = (1 << 0) | (1 << 1) | (1 << 2) | (1 << 3) | (1 << 8)
     err = w.start(mask)
@@ -1358,7 +1368,7 @@ def test_xgmi_link_state_on_real_mi355x(inv):
     for g in gpus:
         assert g["status_ok"], g
         assert sum(s == LINK_UP for s in g["status"]) >= 1, g
-        if g["metrics_ok"]:
+        if g["metrics_ok"] and len(mine) > 1:     # a peer among this node's GPUs takes a second GPU
             assert any(p["peer_bdf"].lower() in mine and p["link_type"] == 2 for p in g["peers"]), g
     w = FabricWatcher(inv)
     w.check()

@@ -53,7 +53,12 @@ def _present_kfd_entries():
     namespace (the gpurun box) does not show as os.getpid(): this pytest
     process, which may hold HIP queues from earlier GPU tests, is among them."""
     root = "/sys/class/kfd/kfd/proc"
-    return sorted(os.listdir(root)) if os.path.isdir(root) else []
+    if os.path.isdir(root):
+        return sorted(os.listdir(root))
+    # a kfd without a process list (some guests): the engine then tells the GPU's
+    # processes by their open device nodes, under the PIDs this namespace shows
+    from rocm_k8s_device_plugin_amd.testing.kfd_caps import kfd_holders
+    return kfd_holders()
 
 
 def _engine(ordinals, **opts):
@@ -97,6 +102,7 @@ def test_native_engine_live_devices_keep_their_identity(inv, ordinals):
 def test_native_kept_queue_server_is_not_a_tenant(inv, ordinals):
     """The kept-queue server's own kfd entry is found and excluded: its queue on
     the GPU does not make the GPU look busy to the engine."""
+    from rocm_k8s_device_plugin_amd.testing.kfd_caps import kfd_process_list_present
     from rocm_k8s_device_plugin_amd.topology import kfd_busy_gpu_ids
     dev_id = min(ordinals, key=ordinals.get)
     gid = inv.topology.node(inv.by_id[dev_id].node_id).gpu_id
@@ -105,6 +111,14 @@ def test_native_kept_queue_server_is_not_a_tenant(inv, ordinals):
     try:
         eng.sweep()
         assert eng.snapshot()[dev_id][0], eng.snapshot()
+        if not kfd_process_list_present():
+            # a kfd without a process list (some guests) has no entry to find: the server's kept
+            # queue still must not make the GPU look busy, and the busy state counts as known
+            assert eng.own_kfd_entries({gid}) == set() and eng.stats()["server_pid"] > 0, eng.stats()
+            eng.sweep()
+            assert eng.stats()["busy_state_known"] and gid not in eng.gpu_load(), (eng.stats(), eng.gpu_load())
+            assert kfd_busy_gpu_ids("/sys") == set()
+            return
         own = eng.own_kfd_entries({gid})
         for _ in range(100):                       # another GPU process started with the server: wait it out
             if own:
@@ -151,7 +165,9 @@ def test_native_probe_server_killed_is_replaced(inv, ordinals):
         res = eng.check(sorted(ordinals), 10.0)
         assert all(r["ok"] or r["pending"] for r in res.values()), res
         deadline = time.monotonic() + 30
-        while own & set(_present_kfd_entries()) and time.monotonic() < deadline:
+        from rocm_k8s_device_plugin_amd.testing.kfd_caps import kfd_process_list_present
+        dying = own if kfd_process_list_present() else {str(st["server_pid"])}   # no list: the killed PID itself
+        while dying & set(_present_kfd_entries()) and time.monotonic() < deadline:
             time.sleep(0.1)
         res = eng.check(sorted(ordinals), 10.0)
         assert all(r["ok"] for r in res.values()), res
@@ -218,6 +234,11 @@ def test_native_daemon_admission_with_smi_sources(inv, ordinals, tmp_path):
             return {k: float(v) for k, v in (ln.rsplit(" ", 1) for ln in r.read().decode().splitlines()
                                              if ln and not ln.startswith("#"))}
 
+    # kfd without SMI events (some guests): the daemon must say so once, count that source's
+    # readings as errors and go on with every other source
+    from rocm_k8s_device_plugin_amd.testing.kfd_caps import kfd_smi_events_refused
+    events_refused = kfd_smi_events_refused(inv.topology.node(inv.by_id[min(ordinals, key=ordinals.get)].node_id).gpu_id)
+
     def reading(m, source, result):
         return sum(v for k, v in m.items() if k.startswith("mi355x_dp_health_source_readings_total{")
                    and f'source="{source}"' in k and f'result="{result}"' in k)
@@ -236,7 +257,8 @@ def test_native_daemon_admission_with_smi_sources(inv, ordinals, tmp_path):
             await asyncio.sleep(2.5)                              # two more pulses
             m = await asyncio.to_thread(metrics)
             for source in ("kfd", "liveness", "smi_ecc", "smi_events", "smi_xgmi"):
-                assert reading(m, source, "ok") >= 2 and reading(m, source, "error") == 0, (source, {
+                good, bad = ("error", "ok") if source == "smi_events" and events_refused else ("ok", "error")
+                assert reading(m, source, good) >= 2 and reading(m, source, bad) == 0, (source, {
                     k: v for k, v in m.items() if "source_readings" in k})
             adm = await k.admit("amd.com/gpu", 1)                 # PreStartContainer included
             car = adm.response.container_responses[0]
@@ -266,7 +288,7 @@ def test_native_daemon_admission_with_smi_sources(inv, ordinals, tmp_path):
         return err.decode(errors="replace")
 
     err = asyncio.run(asyncio.wait_for(go(), 240))
-    assert "amd-smi event notification unavailable" not in err, err[-2000:]
+    assert ("amd-smi event notification unavailable" in err) == bool(events_refused), (events_refused, err[-2000:])
     os.makedirs("gpurun_out", exist_ok=True)
     with open("gpurun_out/native_daemon_smi_sources.log", "w") as f:
         f.write(err[-20000:])

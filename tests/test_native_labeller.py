@@ -423,7 +423,15 @@ def test_real_node_labels_equal_the_python_labeller():
     # counts against the raw sysfs, not only the twin: every amdgpu PCI function is
     # counted in device-id, and in vram / cu-count / simd-count too (kfd-denied
     # GPUs from PCI sysfs); the readable kfd GPU nodes are a subset
-    pci = [b for b in os.listdir("/sys/module/amdgpu/drivers/pci:amdgpu") if b.count(":") == 2]
+    drv = "/sys/module/amdgpu/drivers/pci:amdgpu"
+    if os.path.isdir(drv):
+        pci = [b for b in os.listdir(drv) if b.count(":") == 2]
+    else:   # a guest without the driver's directory: the AMD functions that carry drm nodes
+        pci = []
+        for b in os.listdir("/sys/bus/pci/devices"):
+            with open(f"/sys/bus/pci/devices/{b}/vendor") as f:
+                if f.read().strip() == "0x1002" and os.path.isdir(f"/sys/bus/pci/devices/{b}/drm"):
+                    pci.append(b)
     readable = []
     for n in os.listdir("/sys/class/kfd/kfd/topology/nodes"):
         try:

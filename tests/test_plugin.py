@@ -1011,6 +1011,7 @@ def test_busy_unknown_uses_the_short_grace(tmp_path, monkeypatch):
         raise M.KfdBusyUnknown("proc: Permission denied")
 
     monkeypatch.setattr(M, "kfd_busy_gpu_ids", unknown)
+    monkeypatch.setattr(M, "kfd_gpu_load", unknown)      # what the liveness pass reads
     ctl, prober = _stub_prober(tmp_path, {"3": "pending"})
     mon = HealthMonitor(inv, HealthConfig(exporter_socket=None, liveness=True, fail_threshold=2,
                                           liveness_busy_grace_s=300.0, liveness_unknown_busy_grace_s=0.0),

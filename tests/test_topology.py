@@ -167,3 +167,32 @@ def test_hip_ordinals_follow_kfd_node_order(tmp_path):
     if os.getuid() != 0:  # root ignores permission bits
         ords2 = hip_ordinals(inv, str(fi.dev))
         assert by_node[0].id not in ords2 and ords2[by_node[1].id] == 0
+
+
+def test_guest_without_the_driver_directory(tmp_path):
+    """A guest that is handed its GPU without amdgpu's module view: no
+    module/amdgpu/drivers, no bus/pci/drivers/amdgpu, no driver link on the
+    function; kfd, drm and the function's own attributes are there. The same
+    devices, fingerprint and partition support as with the driver directory;
+    a function without a render node (vfio-pci's) is not amdgpu's."""
+    from rocm_k8s_device_plugin_amd.ops.native import core
+    from rocm_k8s_device_plugin_amd.topology import topology_signature
+    fi = make_mi355x_node(tmp_path, num_gpus=2, compute_partition="dpx")
+    base = str(fi.sysfs)
+    with_driver = discover(base)
+    sig = topology_signature(base)
+    shutil.rmtree(fi.sysfs / "module/amdgpu/drivers")
+    shutil.rmtree(fi.sysfs / "bus/pci/drivers/amdgpu")
+    for b in fi.bdfs:
+        os.unlink(fi.sysfs / "devices/pci0000:00" / b / "driver")
+    inv = discover(base)
+    assert inv.driver_loaded and inv.devices == with_driver.devices and len(inv) == 4
+    assert not any("driver unavailable" in w for w in inv.warnings)
+    assert topology_signature(base) == sig
+    assert inv.compute_partition_supported() and inv.memory_partition_supported()
+    assert core().amdgpu_driver_visible(base)
+    assert hip_ordinals(inv, str(fi.dev)) == hip_ordinals(with_driver, str(fi.dev))
+    shutil.rmtree(fi.sysfs / "devices/pci0000:00" / fi.bdfs[1] / "drm")
+    assert [b for b, _ in core().amdgpu_pci_functions(base)] == [fi.bdfs[0]]
+    shutil.rmtree(fi.sysfs / "devices/pci0000:00" / fi.bdfs[0] / "drm")
+    assert not core().amdgpu_driver_visible(base) and not discover(base).driver_loaded
