@@ -408,6 +408,50 @@ int mi355x_hsa_datapath_f16_check(int ordinal, uint32_t nonce, double timeout_s,
 // Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later f16 check (stage 0..6).
 void mi355x_hsa_datapath_f16_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- f64 MFMA datapath check (64-bit operands and accumulators, bit-exact) -----
+// The same shape for doubles: nine v_mfma_f64_16x16x4_f64 (two one-hot stages
+// of two passes, the second on complemented operands, a stage whose outputs
+// are exact 53-bit products, a sum stage, and the three neg forms of a sum
+// stage) and three v_mfma_f64_4x4x4_4b_f64 per wave, on operands for which
+// every product and every partial sum, in any order, is an exact double
+// (datapath_f64_kernel.h). Each wave checks its accumulators, as 32-bit words,
+// against a VALU fma recomputation; the host checks wave 0's twelve tiles of
+// every workgroup word for word in integer arithmetic. The fields have the int8
+// check's meanings (mfma_bad counts 32-bit words); stage_bad has 7 entries.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[7];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;     // within the stage: (tile * doubles of a tile + double) * 2 + high word
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double kernel_us;
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_f64_result;
+
+int mi355x_hsa_datapath_f64_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_f64_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later f64 check (stage 0..6).
+void mi355x_hsa_datapath_f64_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

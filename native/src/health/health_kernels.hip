@@ -7,3 +7,4 @@
 #include "datapath_bf16_kernel.hip"
 #include "datapath_fp8_kernel.hip"
 #include "datapath_f16_kernel.hip"
+#include "datapath_f64_kernel.hip"
