@@ -452,6 +452,50 @@ int mi355x_hsa_datapath_f64_check(int ordinal, uint32_t nonce, double timeout_s,
 // Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later f64 check (stage 0..6).
 void mi355x_hsa_datapath_f64_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- fp6 / fp4 MX-scaled MFMA datapath check (192- and 128-bit operands, bit-exact) -----
+// The same shape for the narrow formats of the MX-scaled forms: six
+// v_mfma_scale_f32_32x32x64_f8f6f4 and two v_mfma_scale_f32_16x16x128_f8f6f4
+// per wave with e2m3, e3m2 and e2m1 operands of 6 and 4 dwords (and e4m3 by
+// e2m1, the MXFP4-weights pairing), four one-hot stages and four product stages
+// on operands and E8M0 scales for which every partial sum, in any order, is an
+// exact f32 (datapath_f6f4_kernel.h). Each wave checks its accumulators, as
+// words, against a VALU fmaf recomputation over integer-decoded operands; the
+// host checks wave 0's eight tiles of every workgroup word for word. The fields
+// have the int8 check's meanings; stage_bad has 8 entries.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[8];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;     // row * dim + col of the stage's tile
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double kernel_us;
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_f6f4_result;
+
+int mi355x_hsa_datapath_f6f4_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_f6f4_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later f6f4 check (stage 0..7).
+void mi355x_hsa_datapath_f6f4_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

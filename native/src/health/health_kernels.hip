@@ -8,3 +8,4 @@
 #include "datapath_fp8_kernel.hip"
 #include "datapath_f16_kernel.hip"
 #include "datapath_f64_kernel.hip"
+#include "datapath_f6f4_kernel.hip"

@@ -4,7 +4,7 @@ GPU would have left behind, and the shipped host verdict on them.
 The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
 (chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h,
-datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h) says the same of the
+datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h, datapath_f6f4_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -24,6 +24,7 @@ from . import datapath_bf16_reference as dpbf
 from . import datapath_fp8_reference as dpf8
 from . import datapath_f16_reference as dphf
 from . import datapath_f64_reference as dpd
+from . import datapath_f6f4_reference as dpf6
 from . import datapath_i8_reference as dpi8
 from . import datapath_reference as dp
 from . import kernel_reference as ref
@@ -51,10 +52,10 @@ DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad"
                  "xccs_covered", "error")
 KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
         "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS, "datapath_f16": DATAPATH_KEYS,
-        "datapath_f64": DATAPATH_KEYS}
+        "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
          "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES,
-         "datapath_f64": DATAPATH_MODES}
+         "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -186,6 +187,30 @@ def datapath_f64_replies(build_dir) -> list:
     return out
 
 
+def datapath_f6f4_replies(build_dir) -> list:
+    """As _datapath_case, on stage 4 (the first product stage, 1024 words): the shipped verdict's device objects for the
+    modes, on the header's own image (datapath_f6f4_contract_cli image)."""
+    cli = contract_cli.datapath_f6f4_cli(build_dir)
+    healthy = np.frombuffer(contract_cli.datapath_f6f4_image(cli, GRID, NONCE), dtype="<u4")
+    out = []
+    for mode in MODES["datapath_f6f4"]:
+        recs = healthy[:GRID * dpf6.REC_WORDS].reshape(GRID, dpf6.REC_WORDS).copy()
+        tiles = healthy[GRID * dpf6.REC_WORDS:].reshape(GRID, dpf6.WG_WORDS).copy()
+        lo = dpf6.TILE_OFFSET[4]
+        if mode == "stuck_bit":
+            tiles[WG, lo:lo + dpf6.STAGE_WORDS[4]] &= np.uint32(~(1 << BIT) & 0xFFFFFFFF)
+        elif mode == "missing":
+            recs[WG:WG + 2, :] = 0
+        elif mode == "device_bad":
+            recs[WG, dpf6.REC_BAD + 4] = 12
+        else:
+            assert mode == "ok", mode
+        r = contract_cli.datapath_f6f4_verdict(cli, dpf6.image_bytes(recs, tiles), GRID, NONCE, build_dir)
+        assert r.returncode == 0, r.stderr
+        out.append(json.loads(r.stdout))
+    return out
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -209,6 +234,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = dphf.verdicts(cli, [datapath_f16_case(m, image) for m in modes], len(modes))
     elif kind == "datapath_f64":
         out = datapath_f64_replies(build_dir)
+    elif kind == "datapath_f6f4":
+        out = datapath_f6f4_replies(build_dir)
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:
