@@ -48,7 +48,7 @@ py::dict to_dict(const mi355x_probe_result& r) {
 }  // namespace
 
 // mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result / _f16_result / _f64_result /
-// _f6f4_result (the same
+// _f6f4_result / _sparse_result (the same
 // fields; stage_bad differs in length)
 template <typename R>
 py::dict datapath_dict(const R& r) {
@@ -238,6 +238,17 @@ PYBIND11_MODULE(_hip, m) {
         {
           py::gil_scoped_release nogil;
           mi355x_hsa_datapath_f6f4_check(ordinal, nonce, timeout_s, &r);
+        }
+        return datapath_dict(r);
+      },
+      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+  m.def(
+      "hsa_datapath_sparse_check",
+      [](int ordinal, uint32_t nonce, double timeout_s) {
+        mi355x_datapath_sparse_result r;
+        {
+          py::gil_scoped_release nogil;
+          mi355x_hsa_datapath_sparse_check(ordinal, nonce, timeout_s, &r);
         }
         return datapath_dict(r);
       },

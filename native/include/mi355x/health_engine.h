@@ -215,6 +215,8 @@ struct Config {
   int datapath_f64_check_every = 0;
   // and for the fp6 / fp4 MX-scaled MFMA datapath check, likewise (0 = off)
   int datapath_f6f4_check_every = 0;
+  // and for the sparse (2:4) MFMA datapath check, likewise (0 = off)
+  int datapath_sparse_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_hbm_write_gbps = 2000.0;
   double perf_min_mfma_tflops = 700.0;
@@ -301,6 +303,10 @@ class Engine {
   uint64_t datapath_f6f4_failures() const { return datapath_f6f4_.failures; }
   // and for the fp6 / fp4 MX-scaled MFMA datapath check
   std::map<std::string, std::string> datapath_f6f4_failed() const;
+  uint64_t datapath_sparse_checks() const { return datapath_sparse_.checks; }
+  uint64_t datapath_sparse_failures() const { return datapath_sparse_.failures; }
+  // and for the sparse (2:4) MFMA datapath check
+  std::map<std::string, std::string> datapath_sparse_failed() const;
   // device -> (ok | degraded | failed, reason) of its last throughput check
   std::map<std::string, std::pair<std::string, std::string>> perf_verdicts() const;
   std::map<std::string, ProbeOutcome> perf_last() const;  // device -> its last throughput-check reply
@@ -353,9 +359,9 @@ class Engine {
     uint64_t checks = 0, failures = 0;
     std::map<std::string, std::string> failed;  // guarded by mu_
   };
-  struct DatapathKind;  // the f32, int8, bf16, fp8, f16, f64 or f6f4 check: request verb, wording, series names
+  struct DatapathKind;  // the f32, int8, bf16, fp8, f16, f64, f6f4 or sparse check: request verb, wording, series names
   static const DatapathKind kDatapathF32, kDatapathI8, kDatapathBf16, kDatapathFp8, kDatapathF16, kDatapathF64,
-      kDatapathF6F4;
+      kDatapathF6F4, kDatapathSparse;
   void datapath_check(const std::map<std::string, int>& ords, const DatapathKind& kind, DatapathState* st);
   SmiXgmiSnapshot read_xgmi();
 
@@ -379,7 +385,7 @@ class Engine {
   std::map<std::string, ProbeOutcome> perf_last_;                     // guarded by mu_
   // each check keeps failures of its own
   DatapathState datapath_, datapath_i8_, datapath_bf16_, datapath_fp8_, datapath_f16_, datapath_f64_,
-      datapath_f6f4_;
+      datapath_f6f4_, datapath_sparse_;
   uint64_t xgmi_readings_ = 0;
   double last_sweep_ms_ = 0;
   int abort_fd_ = -1;

@@ -496,6 +496,52 @@ int mi355x_hsa_datapath_f6f4_check(int ordinal, uint32_t nonce, double timeout_s
 // Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later f6f4 check (stage 0..7).
 void mi355x_hsa_datapath_f6f4_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- sparse (2:4) MFMA datapath check (index operand and B selection, bit-exact) -----
+// The same shape for the structured-sparsity instructions, which no other check
+// issues: ten v_smfmac_* per wave -- v_smfmac_f32_32x32x32_f16 (four stages),
+// 16x16x64_f16, 32x32x32_bf16, 16x16x64_bf16, v_smfmac_i32_32x32x64_i8,
+// 16x16x128_i8 and v_smfmac_f32_32x32x64_fp8_bf8 -- on a compressed A, its index
+// register and a dense B: four selection stages, whose every output names the
+// row of B the index picked, and six sum stages on operands for which every
+// partial sum, in any order, is exact (datapath_sparse_kernel.h). Each wave
+// checks its accumulators, as words, against a VALU recomputation that walks the
+// compressed elements and picks B's row through the same index words; the host
+// checks wave 0's ten tiles of every workgroup word for word. The fields have
+// the int8 check's meanings; stage_bad has 10 entries.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[10];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;     // row * dim + col of the stage's tile
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double kernel_us;
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_sparse_result;
+
+int mi355x_hsa_datapath_sparse_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_sparse_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later sparse check (stage 0..9).
+void mi355x_hsa_datapath_sparse_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

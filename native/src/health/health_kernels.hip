@@ -9,3 +9,4 @@
 #include "datapath_f16_kernel.hip"
 #include "datapath_f64_kernel.hip"
 #include "datapath_f6f4_kernel.hip"
+#include "datapath_sparse_kernel.hip"

@@ -7,7 +7,8 @@
 // 128-bit operands; mi355x_hsa_datapath_fp8_check: fp8 and MX-scaled operands;
 // mi355x_hsa_datapath_f16_check: f16 operands, the legacy 64-bit forms too;
 // mi355x_hsa_datapath_f64_check: f64 operands and accumulators;
-// mi355x_hsa_datapath_f6f4_check: fp6 / fp4 MX-scaled operands), all on the
+// mi355x_hsa_datapath_f6f4_check: fp6 / fp4 MX-scaled operands;
+// mi355x_hsa_datapath_sparse_check: the 2:4 sparse forms, v_smfmac_*), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -34,6 +35,7 @@
 #include "datapath_f6f4_verify.h"
 #include "datapath_fp8_verify.h"
 #include "datapath_i8_verify.h"
+#include "datapath_sparse_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_json.h"
@@ -426,6 +428,7 @@ int g_dpf8_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-fp8, likewise
 int g_dphf_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f16, likewise
 int g_dpd_corrupt[4] = {-1, 0, 0, -1};   // --corrupt-datapath-f64, likewise
 int g_dpf6_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f6f4, likewise
+int g_dpsp_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-sparse, likewise
 
 }  // namespace
 }  // namespace mi355x::hsa_rt
@@ -838,5 +841,50 @@ extern "C" int mi355x_hsa_datapath_f6f4_check(int ordinal, uint32_t nonce, doubl
       tiles[dpf6_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
   }
   mi355x::datapath_f6f4_verdict(records, tiles, grid, out);
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_sparse_corrupt(int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  g_dpsp_corrupt[0] = stage;
+  g_dpsp_corrupt[1] = word;
+  g_dpsp_corrupt[2] = bit;
+  g_dpsp_corrupt[3] = ordinal;
+}
+
+extern "C" int mi355x_hsa_datapath_sparse_check(int ordinal, uint32_t nonce, double timeout_s,
+                                            mi355x_datapath_sparse_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_sparse_result>(ordinal, nonce);
+  Check<mi355x_datapath_sparse_result> c(ordinal, timeout_s, out);
+  KernelInfo k;
+  // no device memory: records, tiles and kernargs all live in host pools
+  if (!c.begin(false, &mi355x_datapath_sparse_result::grid, 1, "datapath_sparse",
+               {{"mi355x_mfma_datapath_sparse.kd", sizeof(mi355x_datapath_sparse_args)}}, &k))
+    return 1;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPSP_REC_WORDS * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPSP_WG_WORDS * sizeof(uint32_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_sparse_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  if (!c.run(k, kargs, grid, MI355X_DPSP_THREADS, "datapath sparse check", &out->kernel_us)) return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = g_dpsp_corrupt;
+    if (cr[0] >= 0 && cr[0] < MI355X_DPSP_STAGES && cr[1] >= 0 &&
+        cr[1] < static_cast<int>(dpsp_dim(cr[0]) * dpsp_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      tiles[dpsp_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
+  }
+  mi355x::datapath_sparse_verdict(records, tiles, grid, out);
   return c.finish();
 }

@@ -66,7 +66,8 @@ def probe_contract_cli(build_dir: Path) -> Path:
 def probe_replies_text(cli, command: str = "replies") -> str:
     """The document `probe_contract_cli replies` (or `replies-bf16`, `replies-fp8`, `replies-f16`) prints, as
     its bytes. The f64 and f6f4 kinds' documents come from `datapath_f64_contract_cli replies` and
-    `datapath_f6f4_contract_cli replies`, likewise."""
+    `datapath_f6f4_contract_cli replies`, and the sparse kind's from
+    `datapath_sparse_contract_cli replies`, likewise."""
     r = subprocess.run([str(cli), command], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     return r.stdout
@@ -126,6 +127,30 @@ def datapath_f6f4_verdict(cli, image: bytes, grid: int, nonce: int, work) -> sub
     """`datapath_f6f4_contract_cli verdict` on `image`, written into the directory `work`: stdout is one
     datapath_f6f4_json line; exit 2 and no line for an image of another length."""
     path = Path(work) / "datapath_f6f4_image.bin"
+    path.write_bytes(image)
+    return subprocess.run([str(cli), "verdict", str(grid), str(nonce), str(path)], capture_output=True, text=True,
+                          timeout=120)
+
+
+def datapath_sparse_cli(build_dir: Path) -> Path:
+    """native/tests/datapath_sparse_contract_cli.cpp, found or compiled like contract_cli()."""
+    from .. import _build
+    exe = _build.DATAPATH_SPARSE_CLI
+    if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
+        return exe
+    return compile_cli(Path(build_dir) / "datapath_sparse_contract_cli",
+                       source=REPO / "native" / "tests" / "datapath_sparse_contract_cli.cpp")
+
+
+def datapath_sparse_image(cli, grid: int, nonce: int) -> bytes:
+    """`datapath_sparse_contract_cli image`: the header's records and tiles, as bytes."""
+    return subprocess.run([str(cli), "image", str(grid), str(nonce)], capture_output=True, check=True, timeout=120).stdout
+
+
+def datapath_sparse_verdict(cli, image: bytes, grid: int, nonce: int, work) -> subprocess.CompletedProcess:
+    """`datapath_sparse_contract_cli verdict` on `image`, written into the directory `work`: stdout is one
+    datapath_sparse_json line; exit 2 and no line for an image of another length."""
+    path = Path(work) / "datapath_sparse_image.bin"
     path.write_bytes(image)
     return subprocess.run([str(cli), "verdict", str(grid), str(nonce), str(path)], capture_output=True, text=True,
                           timeout=120)

@@ -4,7 +4,8 @@ GPU would have left behind, and the shipped host verdict on them.
 The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
 (chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h,
-datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h, datapath_f6f4_verify.h) says the same of the
+datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h, datapath_f6f4_verify.h,
+datapath_sparse_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -26,6 +27,7 @@ from . import datapath_f16_reference as dphf
 from . import datapath_f64_reference as dpd
 from . import datapath_f6f4_reference as dpf6
 from . import datapath_i8_reference as dpi8
+from . import datapath_sparse_reference as dpsp
 from . import datapath_reference as dp
 from . import kernel_reference as ref
 
@@ -52,10 +54,10 @@ DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad"
                  "xccs_covered", "error")
 KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
         "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS, "datapath_f16": DATAPATH_KEYS,
-        "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS}
+        "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS, "datapath_sparse": DATAPATH_KEYS}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
          "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES,
-         "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES}
+         "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES, "datapath_sparse": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -211,6 +213,30 @@ def datapath_f6f4_replies(build_dir) -> list:
     return out
 
 
+def datapath_sparse_replies(build_dir) -> list:
+    """As _datapath_case, on stage 3 (the first sum stage, 1024 words): the shipped verdict's device objects for the
+    modes, on the header's own image (datapath_sparse_contract_cli image)."""
+    cli = contract_cli.datapath_sparse_cli(build_dir)
+    healthy = np.frombuffer(contract_cli.datapath_sparse_image(cli, GRID, NONCE), dtype="<u4")
+    out = []
+    for mode in MODES["datapath_sparse"]:
+        recs = healthy[:GRID * dpsp.REC_WORDS].reshape(GRID, dpsp.REC_WORDS).copy()
+        tiles = healthy[GRID * dpsp.REC_WORDS:].reshape(GRID, dpsp.WG_WORDS).copy()
+        lo = dpsp.TILE_OFFSET[3]
+        if mode == "stuck_bit":
+            tiles[WG, lo:lo + dpsp.STAGE_WORDS[3]] &= np.uint32(~(1 << BIT) & 0xFFFFFFFF)
+        elif mode == "missing":
+            recs[WG:WG + 2, :] = 0
+        elif mode == "device_bad":
+            recs[WG, dpsp.REC_BAD + 3] = 12
+        else:
+            assert mode == "ok", mode
+        r = contract_cli.datapath_sparse_verdict(cli, dpsp.image_bytes(recs, tiles), GRID, NONCE, build_dir)
+        assert r.returncode == 0, r.stderr
+        out.append(json.loads(r.stdout))
+    return out
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -236,6 +262,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = datapath_f64_replies(build_dir)
     elif kind == "datapath_f6f4":
         out = datapath_f6f4_replies(build_dir)
+    elif kind == "datapath_sparse":
+        out = datapath_sparse_replies(build_dir)
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:

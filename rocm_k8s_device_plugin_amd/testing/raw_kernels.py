@@ -19,12 +19,13 @@ REQUESTS.json is a list of requests, run in order:
     {"id": ..., "kernel": "datapath_f16", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
     {"id": ..., "kernel": "datapath_f64", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
     {"id": ..., "kernel": "datapath_f6f4", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
+    {"id": ..., "kernel": "datapath_sparse", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
 
-A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64 or datapath_f6f4 request may add "code_object": "inject": the kernel then comes from
+A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64, datapath_f6f4 or datapath_sparse request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
 the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h /
 datapath_bf16_kernel.h / datapath_fp8_kernel.h / datapath_f16_kernel.h / datapath_f64_kernel.h /
-datapath_f6f4_kernel.h), and may add
+datapath_f6f4_kernel.h / datapath_sparse_kernel.h), and may add
 
     "inject": {"kind": "mfma" | "lds", "wg": w, "wave": v, "lane": l, "index": i, "mask": m}
 
@@ -192,6 +193,21 @@ class DatapathF6F4InjectArgs(ctypes.Structure):
 DATAPATH_F6F4_ARG_STRUCTS = {"mi355x_datapath_f6f4_args": DatapathF6F4Args}
 DATAPATH_F6F4_INJECT_ARG_STRUCTS = {"mi355x_datapath_f6f4_args": DatapathF6F4InjectArgs}
 DATAPATH_F6F4_WG_WORDS = 6 * 32 * 32 + 2 * 16 * 16   # wave 0's eight tiles of one workgroup
+
+
+class DatapathSparseArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("nonce", _u32), ("grid", _u32)]
+
+
+class DatapathSparseInjectArgs(ctypes.Structure):
+    _fields_ = DatapathSparseArgs._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_sparse_kernel.h
+DATAPATH_SPARSE_ARG_STRUCTS = {"mi355x_datapath_sparse_args": DatapathSparseArgs}
+DATAPATH_SPARSE_INJECT_ARG_STRUCTS = {"mi355x_datapath_sparse_args": DatapathSparseInjectArgs}
+DATAPATH_SPARSE_WG_WORDS = 7 * 32 * 32 + 3 * 16 * 16   # wave 0's ten tiles of one workgroup
+DATAPATH_SPARSE_REC_WORDS = 32                       # ten counters do not fit a 16-word record
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -203,7 +219,7 @@ def inject_words(req: dict) -> tuple:
         return (INJECT_KINDS["none"], 0, 0, 0, 0, 0)
     kind = INJECT_KINDS[inj["kind"]]
     if req["kernel"] in ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
-                         "datapath_f16", "datapath_f64", "datapath_f6f4") and inj["kind"] == "lds":
+                         "datapath_f16", "datapath_f64", "datapath_f6f4", "datapath_sparse") and inj["kind"] == "lds":
         raise ValueError("the datapath kernels have no lds injection")
     return (kind, int(inj["wg"]), int(inj.get("wave", 0)), int(inj.get("lane", 0)), int(inj["index"]),
             int(inj["mask"]) & 0xFFFFFFFF)
@@ -214,7 +230,8 @@ def code_object_of(req: dict) -> str:
     if which not in CODE_OBJECTS:
         raise ValueError(f"unknown code object {which!r}")
     if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
-                                                   "datapath_f16", "datapath_f64", "datapath_f6f4"):
+                                                   "datapath_f16", "datapath_f64", "datapath_f6f4",
+                                                   "datapath_sparse"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -230,7 +247,8 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "datapath_fp8": ("mi355x_mfma_datapath_fp8", 256),
            "datapath_f16": ("mi355x_mfma_datapath_f16", 256),
            "datapath_f64": ("mi355x_mfma_datapath_f64", 256),
-           "datapath_f6f4": ("mi355x_mfma_datapath_f6f4", 256)}
+           "datapath_f6f4": ("mi355x_mfma_datapath_f6f4", 256),
+           "datapath_sparse": ("mi355x_mfma_datapath_sparse", 256)}
 
 _H2D, _D2H = 1, 2
 _LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
@@ -414,6 +432,18 @@ def plan(req: dict, base_dir: Path):
         if wgs < g:
             raise ValueError("launch_grid below grid")
         return bufs, lambda p: DatapathF6F4Args(p["records"], p["tiles"], req["nonce"], g), wgs
+    if k == "datapath_sparse":
+        g = int(req["grid"])
+        bufs = [("records", np.uint32, _filled(g * DATAPATH_SPARSE_REC_WORDS * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * DATAPATH_SPARSE_WG_WORDS * 4, OUT_PREFILL))]
+        if code_object_of(req) == "inject":
+            return bufs, lambda p: DatapathSparseInjectArgs(p["records"], p["tiles"], req["nonce"], g,
+                                                           *inject_words(req)), g
+        # the buffers hold `grid` workgroups; the ones launched beyond it must write nothing
+        wgs = int(req.get("launch_grid", g))
+        if wgs < g:
+            raise ValueError("launch_grid below grid")
+        return bufs, lambda p: DatapathSparseArgs(p["records"], p["tiles"], req["nonce"], g), wgs
     raise ValueError(f"unknown kernel {k!r}")
 
 

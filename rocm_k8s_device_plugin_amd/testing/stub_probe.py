@@ -43,6 +43,8 @@ f64 MFMA datapath-check replies ("datapath_f64" requests /
 --datapath-f64) follow the "datapath_f64" map and append "datapath_f64:<host ordinal>".
 fp6 / fp4 MX-scaled MFMA datapath-check replies ("datapath_f6f4" requests /
 --datapath-f6f4) follow the "datapath_f6f4" map and append "datapath_f6f4:<host ordinal>".
+Sparse (2:4) MFMA datapath-check replies ("datapath_sparse" requests /
+--datapath-sparse) follow the "datapath_sparse" map and append "datapath_sparse:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -98,7 +100,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
 
 
 DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16", "datapath_f64",
-                  "datapath_f6f4")
+                  "datapath_f6f4", "datapath_sparse")
 
 
 def _log_check(kind, host_ordinal):
@@ -274,12 +276,30 @@ def _datapath_f6f4_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 8, stuck, 300.0, 3000.0, kind="datapath_f6f4")
 
 
+# the shipped verdict's figures for that fault at nonce 0x5EED142F: wrong words, the first of them, its healthy value
+STUCK_SPARSE = (540, 1, 3250552640)
+
+
+def _datapath_sparse_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """Sparse (2:4) MFMA datapath-check reply (kind "datapath_sparse"; ten stages); the
+    modes of _datapath_device, from the control file's "datapath_sparse" map
+    (stuck_bit: bit 30 of every stage-3 word of one CU's tile)."""
+    stuck = dict(records_ok=255, tile_bad=STUCK_SPARSE[0], first_bad_wg=17, first_bad_stage=3,
+                 first_bad_word=STUCK_SPARSE[1], first_bad_got=STUCK_SPARSE[2] ^ 0x40000000,
+                 first_bad_want=STUCK_SPARSE[2], first_bad_xor=0x40000000,
+                 error=f"255/256 workgroups exact (device_bad=0 tile_bad={STUCK_SPARSE[0]}); first bad: wg 17 stage 3 "
+                       f"word {STUCK_SPARSE[1]} xor 0x40000000 (bit 30)")
+    return _datapath_reply(ordinal_reported, mode, nonce, host_ordinal, 10, stuck, 400.0, 3200.0,
+                           kind="datapath_sparse")
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
                 "datapath_fp8": _datapath_fp8_device,
                 "datapath_f16": _datapath_f16_device,
                 "datapath_f64": _datapath_f64_device,
-                "datapath_f6f4": _datapath_f6f4_device}
+                "datapath_f6f4": _datapath_f6f4_device,
+                "datapath_sparse": _datapath_sparse_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -354,6 +374,7 @@ _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapa
           ("datapath_f16", (_FLOAT,)),
           ("datapath_f64", (_FLOAT,)),
           ("datapath_f6f4", (_FLOAT,)),
+          ("datapath_sparse", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -647,6 +668,7 @@ def main(argv):
                        ("--datapath-f16", "datapath_f16"),
                        ("--datapath-f64", "datapath_f64"),
                        ("--datapath-f6f4", "datapath_f6f4"),
+                       ("--datapath-sparse", "datapath_sparse"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
