@@ -48,7 +48,7 @@ py::dict to_dict(const mi355x_probe_result& r) {
 }  // namespace
 
 // mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result / _f16_result / _f64_result /
-// _f6f4_result / _sparse_result (the same
+// _f6f4_result / _sparse_result / _gemm_result (the same
 // fields; stage_bad differs in length)
 template <typename R>
 py::dict datapath_dict(const R& r) {
@@ -251,6 +251,20 @@ PYBIND11_MODULE(_hip, m) {
           mi355x_hsa_datapath_sparse_check(ordinal, nonce, timeout_s, &r);
         }
         return datapath_dict(r);
+      },
+      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+  m.def(
+      "hsa_datapath_gemm_check",
+      [](int ordinal, uint32_t nonce, double timeout_s) {
+        mi355x_datapath_gemm_result r;
+        {
+          py::gil_scoped_release nogil;
+          mi355x_hsa_datapath_gemm_check(ordinal, nonce, timeout_s, &r);
+        }
+        py::dict d = datapath_dict(r);
+        d["ksteps"] = r.ksteps;
+        d["fill_us"] = r.fill_us;
+        return d;
       },
       py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
 }

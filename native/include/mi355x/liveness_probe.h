@@ -542,6 +542,58 @@ int mi355x_hsa_datapath_sparse_check(int ordinal, uint32_t nonce, double timeout
 // Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later sparse check (stage 0..9).
 void mi355x_hsa_datapath_sparse_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- bf16 GEMM pipeline check (HBM to LDS to MFMA chains, bit-exact) -----
+// The datapath checks above build operands in registers and issue one MFMA per
+// stage. This one is a small real GEMM (datapath_gemm_kernel.h): mi355x_gemm_fill
+// writes a bf16 A panel per workgroup and one shared B panel into device memory,
+// and mi355x_mfma_datapath_gemm, one workgroup per CU, moves them into LDS with
+// the direct-to-LDS loads (global_load_lds_dwordx4), out of it with 128-bit and
+// transposed (ds_read_b64_tr_b16) reads, and through dependent chains of
+// 4 * ksteps v_mfma_f32_32x32x16_bf16 per accumulator while the next tile's
+// loads are in flight. The operands make every partial sum exact in any order,
+// so the host checks every D word exactly (datapath_gemm_verify.h) and, per wave,
+// a fold of the fragments that came out of LDS. stage_bad: wrong fold words of
+// the A feed, of the B feed, wrong D words; mfma_bad = the feeds' sum, tile_bad
+// = the D words. first_bad_word: the wave's fold word (wave * 2 + {xor, sum})
+// for stages 0 and 1, row * 128 + column for stage 2.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int ksteps;             // K / 64
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[3];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double fill_us;         // GPU time of mi355x_gemm_fill
+  double kernel_us;       // GPU time of mi355x_mfma_datapath_gemm
+  double verify_us;       // host time of the verdict
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_gemm_result;
+
+int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_gemm_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later GEMM check: bit `bit` of word `word` of
+// workgroup 0's stage-`stage` data (0: A fold word, 1: B fold word, 2: D word) is flipped before the verdict.
+void mi355x_hsa_datapath_gemm_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,3 +10,4 @@
 #include "datapath_f64_kernel.hip"
 #include "datapath_f6f4_kernel.hip"
 #include "datapath_sparse_kernel.hip"
+#include "datapath_gemm_kernel.hip"

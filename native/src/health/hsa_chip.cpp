@@ -8,7 +8,8 @@
 // mi355x_hsa_datapath_f16_check: f16 operands, the legacy 64-bit forms too;
 // mi355x_hsa_datapath_f64_check: f64 operands and accumulators;
 // mi355x_hsa_datapath_f6f4_check: fp6 / fp4 MX-scaled operands;
-// mi355x_hsa_datapath_sparse_check: the 2:4 sparse forms, v_smfmac_*), all on the
+// mi355x_hsa_datapath_sparse_check: the 2:4 sparse forms, v_smfmac_*;
+// mi355x_hsa_datapath_gemm_check: a bf16 GEMM out of HBM through LDS), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -35,6 +36,7 @@
 #include "datapath_f6f4_verify.h"
 #include "datapath_fp8_verify.h"
 #include "datapath_i8_verify.h"
+#include "datapath_gemm_verify.h"
 #include "datapath_sparse_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
@@ -429,6 +431,7 @@ int g_dphf_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f16, likewise
 int g_dpd_corrupt[4] = {-1, 0, 0, -1};   // --corrupt-datapath-f64, likewise
 int g_dpf6_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f6f4, likewise
 int g_dpsp_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-sparse, likewise
+int g_dpgm_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-gemm, likewise
 
 }  // namespace
 }  // namespace mi355x::hsa_rt
@@ -886,5 +889,64 @@ extern "C" int mi355x_hsa_datapath_sparse_check(int ordinal, uint32_t nonce, dou
       tiles[dpsp_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
   }
   mi355x::datapath_sparse_verdict(records, tiles, grid, out);
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_gemm_corrupt(int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  g_dpgm_corrupt[0] = stage;
+  g_dpgm_corrupt[1] = word;
+  g_dpgm_corrupt[2] = bit;
+  g_dpgm_corrupt[3] = ordinal;
+}
+
+extern "C" int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, double timeout_s,
+                                              mi355x_datapath_gemm_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_gemm_result>(ordinal, nonce);
+  out->ksteps = MI355X_DPGM_KSTEPS;
+  Check<mi355x_datapath_gemm_result> c(ordinal, timeout_s, out);
+  KernelInfo ks[2];  // fill, gemm
+  // the operands live in device memory; records, D tiles and kernargs in host pools
+  if (!c.begin(true, &mi355x_datapath_gemm_result::grid, 1, "datapath_gemm",
+               {{"mi355x_gemm_fill.kd", sizeof(mi355x_datapath_gemm_args)},
+                {"mi355x_mfma_datapath_gemm.kd", sizeof(mi355x_datapath_gemm_args)}},
+               ks))
+    return 1;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
+  const size_t K = static_cast<size_t>(MI355X_DPGM_KSTEPS) * MI355X_DPGM_KSTEP;
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPGM_REC_WORDS * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPGM_WG_WORDS * sizeof(uint32_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  // written by mi355x_gemm_fill, whole, before the GEMM reads them: no runtime fill or copy (ROCr would open a queue)
+  auto* a = c.bufs.alloc<uint16_t>(c.ag->coarse, grid * MI355X_DPGM_TILE * K * sizeof(uint16_t), "alloc A");
+  auto* b = c.bufs.alloc<uint16_t>(c.ag->coarse, K * MI355X_DPGM_TILE * sizeof(uint16_t), "alloc B");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_gemm_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->a = a;
+  kargs->b = b;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  kargs->ksteps = MI355X_DPGM_KSTEPS;
+  if (!c.run(ks[0], kargs, grid, MI355X_DPGM_THREADS, "datapath gemm fill", &out->fill_us) ||
+      !c.run(ks[1], kargs, grid, MI355X_DPGM_THREADS, "datapath gemm check", &out->kernel_us))
+    return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = g_dpgm_corrupt;
+    const int words = cr[0] == 2 ? MI355X_DPGM_WG_WORDS : 8;
+    if (cr[0] >= 0 && cr[0] < MI355X_DPGM_STAGES && cr[1] >= 0 && cr[1] < words && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      (cr[0] == 2 ? tiles[cr[1]] : records[dpgm_fold_slot(cr[0], cr[1])]) ^= 1u << cr[2];
+  }
+  const auto t_verify = std::chrono::steady_clock::now();
+  mi355x::datapath_gemm_verdict(records, tiles, grid, MI355X_DPGM_KSTEPS, out);
+  out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
 }

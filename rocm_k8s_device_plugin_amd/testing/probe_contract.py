@@ -5,7 +5,7 @@ The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
 (chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h,
 datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h, datapath_f6f4_verify.h,
-datapath_sparse_verify.h) says the same of the
+datapath_sparse_verify.h, datapath_gemm_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -28,6 +28,7 @@ from . import datapath_f64_reference as dpd
 from . import datapath_f6f4_reference as dpf6
 from . import datapath_i8_reference as dpi8
 from . import datapath_sparse_reference as dpsp
+from . import datapath_gemm_reference as dpgm
 from . import datapath_reference as dp
 from . import kernel_reference as ref
 
@@ -54,10 +55,12 @@ DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad"
                  "xccs_covered", "error")
 KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
         "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS, "datapath_f16": DATAPATH_KEYS,
-        "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS, "datapath_sparse": DATAPATH_KEYS}
+        "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS, "datapath_sparse": DATAPATH_KEYS,
+        "datapath_gemm": DATAPATH_KEYS}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
          "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES,
-         "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES, "datapath_sparse": DATAPATH_MODES}
+         "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES, "datapath_sparse": DATAPATH_MODES,
+         "datapath_gemm": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -237,6 +240,30 @@ def datapath_sparse_replies(build_dir) -> list:
     return out
 
 
+def datapath_gemm_replies(build_dir) -> list:
+    """As _datapath_case for the GEMM pipeline check at the production K: the shipped verdict's device objects for the
+    modes, on the header's own image. stuck_bit: bit 30 of every D word of row 0 of one workgroup; device_bad: that
+    workgroup's first A fold word is off by 12."""
+    cli = contract_cli.datapath_gemm_cli(build_dir)
+    healthy = np.frombuffer(contract_cli.datapath_gemm_image(cli, GRID, NONCE, dpgm.KSTEPS), dtype="<u4")
+    out = []
+    for mode in MODES["datapath_gemm"]:
+        recs = healthy[:GRID * dpgm.REC_WORDS].reshape(GRID, dpgm.REC_WORDS).copy()
+        tiles = healthy[GRID * dpgm.REC_WORDS:].reshape(GRID, dpgm.WG_WORDS).copy()
+        if mode == "stuck_bit":
+            tiles[WG, :dpgm.TILE] &= np.uint32(~(1 << BIT) & 0xFFFFFFFF)
+        elif mode == "missing":
+            recs[WG:WG + 2, :] = 0
+        elif mode == "device_bad":
+            recs[WG, dpgm.fold_slot(0, 1)] += 12
+        else:
+            assert mode == "ok", mode
+        r = contract_cli.datapath_gemm_verdict(cli, dpgm.image_bytes(recs, tiles), GRID, NONCE, dpgm.KSTEPS, build_dir)
+        assert r.returncode == 0, r.stderr
+        out.append(json.loads(r.stdout))
+    return out
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -264,6 +291,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = datapath_f6f4_replies(build_dir)
     elif kind == "datapath_sparse":
         out = datapath_sparse_replies(build_dir)
+    elif kind == "datapath_gemm":
+        out = datapath_gemm_replies(build_dir)
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:

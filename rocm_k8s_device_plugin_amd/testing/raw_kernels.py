@@ -20,6 +20,10 @@ REQUESTS.json is a list of requests, run in order:
     {"id": ..., "kernel": "datapath_f64", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
     {"id": ..., "kernel": "datapath_f6f4", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
     {"id": ..., "kernel": "datapath_sparse", "nonce": n, "grid": g[, "launch_grid": workgroups launched, >= g]}
+    {"id": ..., "kernel": "datapath_gemm", "nonce": n, "grid": g, "ksteps": k[, "launch_grid": ...]}
+        (mi355x_gemm_fill, then mi355x_mfma_datapath_gemm, on the same arguments; with the inject build
+        "inject" may also be {"kind": "lds", "wg": w, "step": s, "index": LDS dword of the step's buffer, "mask": m}
+        or {"kind": "hbm", "wg": w, "index": row * K + k of A, "mask": m})
 
 A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64, datapath_f6f4 or datapath_sparse request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
@@ -208,6 +212,23 @@ DATAPATH_SPARSE_ARG_STRUCTS = {"mi355x_datapath_sparse_args": DatapathSparseArgs
 DATAPATH_SPARSE_INJECT_ARG_STRUCTS = {"mi355x_datapath_sparse_args": DatapathSparseInjectArgs}
 DATAPATH_SPARSE_WG_WORDS = 7 * 32 * 32 + 3 * 16 * 16   # wave 0's ten tiles of one workgroup
 DATAPATH_SPARSE_REC_WORDS = 32                       # ten counters do not fit a 16-word record
+
+
+class DatapathGemmArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("a", _ptr), ("b", _ptr), ("nonce", _u32), ("grid", _u32),
+                ("ksteps", _u32), ("pad", _u32)]
+
+
+class DatapathGemmInjectArgs(ctypes.Structure):
+    _fields_ = DatapathGemmArgs._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_gemm_kernel.h; both kernels of the check take the one struct
+DATAPATH_GEMM_ARG_STRUCTS = {"mi355x_datapath_gemm_args": DatapathGemmArgs}
+DATAPATH_GEMM_INJECT_ARG_STRUCTS = {"mi355x_datapath_gemm_args": DatapathGemmInjectArgs}
+DATAPATH_GEMM_WG_WORDS = 128 * 128                   # the whole D tile of one workgroup
+DATAPATH_GEMM_REC_WORDS = 32
+DATAPATH_GEMM_INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2, "hbm": 3}   # MI355X_DPGM_INJECT_*
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -217,6 +238,9 @@ def inject_words(req: dict) -> tuple:
     inj = req.get("inject")
     if inj is None:
         return (INJECT_KINDS["none"], 0, 0, 0, 0, 0)
+    if req["kernel"] == "datapath_gemm":                 # the wave field carries the step of an lds injection
+        return (DATAPATH_GEMM_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj.get("wave", inj.get("step", 0))),
+                int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
     kind = INJECT_KINDS[inj["kind"]]
     if req["kernel"] in ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                          "datapath_f16", "datapath_f64", "datapath_f6f4", "datapath_sparse") and inj["kind"] == "lds":
@@ -231,7 +255,7 @@ def code_object_of(req: dict) -> str:
         raise ValueError(f"unknown code object {which!r}")
     if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                                                    "datapath_f16", "datapath_f64", "datapath_f6f4",
-                                                   "datapath_sparse"):
+                                                   "datapath_sparse", "datapath_gemm"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -248,7 +272,10 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "datapath_f16": ("mi355x_mfma_datapath_f16", 256),
            "datapath_f64": ("mi355x_mfma_datapath_f64", 256),
            "datapath_f6f4": ("mi355x_mfma_datapath_f6f4", 256),
-           "datapath_sparse": ("mi355x_mfma_datapath_sparse", 256)}
+           "datapath_sparse": ("mi355x_mfma_datapath_sparse", 256),
+           "datapath_gemm": ("mi355x_mfma_datapath_gemm", 256)}
+# kernel -> (symbol, lanes) of a kernel launched before it, on the same arguments and workgroups
+FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256)}
 
 _H2D, _D2H = 1, 2
 _LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
@@ -444,6 +471,21 @@ def plan(req: dict, base_dir: Path):
         if wgs < g:
             raise ValueError("launch_grid below grid")
         return bufs, lambda p: DatapathSparseArgs(p["records"], p["tiles"], req["nonce"], g), wgs
+    if k == "datapath_gemm":
+        g, ksteps = int(req["grid"]), int(req["ksteps"])
+        if not 1 <= ksteps <= 32:
+            raise ValueError("ksteps outside 1..32")        # the operand buffers are sized by it
+        bufs = [("records", np.uint32, _filled(g * DATAPATH_GEMM_REC_WORDS * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * DATAPATH_GEMM_WG_WORDS * 4, OUT_PREFILL)),
+                ("a", np.uint16, _filled(g * 128 * ksteps * 64 * 2, OUT_PREFILL)),
+                ("b", np.uint16, _filled(ksteps * 64 * 128 * 2, OUT_PREFILL))]
+        if code_object_of(req) == "inject":
+            return bufs, lambda p: DatapathGemmInjectArgs(p["records"], p["tiles"], p["a"], p["b"], req["nonce"], g,
+                                                          ksteps, 0, *inject_words(req)), g
+        wgs = int(req.get("launch_grid", g))
+        if wgs < g:
+            raise ValueError("launch_grid below grid")
+        return bufs, lambda p: DatapathGemmArgs(p["records"], p["tiles"], p["a"], p["b"], req["nonce"], g, ksteps, 0), wgs
     raise ValueError(f"unknown kernel {k!r}")
 
 
@@ -457,6 +499,9 @@ def run_request(hip: Hip, functions: dict, req: dict, base_dir: Path, outdir: Pa
     extra = (ctypes.c_void_p * 5)(_LAUNCH_PARAM_BUFFER_POINTER, ctypes.addressof(args), _LAUNCH_PARAM_BUFFER_SIZE,
                                   ctypes.addressof(size), _LAUNCH_PARAM_END)
     t0 = time.perf_counter_ns()
+    if req["kernel"] in FIRST:
+        first, first_lanes = FIRST[req["kernel"]]
+        hip.call("hipModuleLaunchKernel", functions[first], wgs, 1, 1, first_lanes, 1, 1, 0, None, None, extra)
     hip.call("hipModuleLaunchKernel", functions[symbol], wgs, 1, 1, lanes, 1, 1, 0, None, None, extra)
     hip.call("hipDeviceSynchronize")
     launch_us = (time.perf_counter_ns() - t0) / 1e3
@@ -474,7 +519,7 @@ def load_functions(hip: Hip, path) -> dict:
     module = ctypes.c_void_p()
     hip.call("hipModuleLoad", ctypes.byref(module), str(path).encode())
     functions = {}
-    for symbol, _ in KERNELS.values():
+    for symbol, _ in list(KERNELS.values()) + list(FIRST.values()):
         f = ctypes.c_void_p()
         hip.call("hipModuleGetFunction", ctypes.byref(f), module, symbol.encode())
         functions[symbol] = f

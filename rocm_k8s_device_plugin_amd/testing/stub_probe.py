@@ -45,6 +45,8 @@ fp6 / fp4 MX-scaled MFMA datapath-check replies ("datapath_f6f4" requests /
 --datapath-f6f4) follow the "datapath_f6f4" map and append "datapath_f6f4:<host ordinal>".
 Sparse (2:4) MFMA datapath-check replies ("datapath_sparse" requests /
 --datapath-sparse) follow the "datapath_sparse" map and append "datapath_sparse:<host ordinal>".
+bf16 GEMM pipeline-check replies ("datapath_gemm" requests /
+--datapath-gemm) follow the "datapath_gemm" map and append "datapath_gemm:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -100,7 +102,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
 
 
 DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16", "datapath_f64",
-                  "datapath_f6f4", "datapath_sparse")
+                  "datapath_f6f4", "datapath_sparse", "datapath_gemm")
 
 
 def _log_check(kind, host_ordinal):
@@ -293,13 +295,42 @@ def _datapath_sparse_device(ordinal_reported, mode, nonce, host_ordinal=None):
                            kind="datapath_sparse")
 
 
+# the shipped verdict's figures for the gemm kind's faults at nonce 0x5EED142F (testing/probe_contract.py builds them):
+# stuck_bit = bit 30 of the 128 D words of row 0 of one workgroup (its first word's healthy value), device_bad = that
+# workgroup's fold word 1 of the A feed off by 12 (its healthy value)
+STUCK_GEMM = (128, 0, 1427601920)
+FEED_GEMM = (1, 2121339312)
+
+
+def _datapath_gemm_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """bf16 GEMM pipeline-check reply (kind "datapath_gemm"; stages: A feed, B feed, D words); the modes of
+    _datapath_device, from the control file's "datapath_gemm" map."""
+    stuck = dict(records_ok=255, tile_bad=STUCK_GEMM[0], stage_bad=[0, 0, STUCK_GEMM[0]], first_bad_wg=17,
+                 first_bad_stage=2, first_bad_word=STUCK_GEMM[1], first_bad_got=STUCK_GEMM[2] ^ 0x40000000,
+                 first_bad_want=STUCK_GEMM[2], first_bad_xor=0x40000000,
+                 error=f"255/256 workgroups exact (feed_bad=0 tile_bad={STUCK_GEMM[0]}); first bad: wg 17 stage 2 "
+                       f"word {STUCK_GEMM[1]} xor 0x40000000 (bit 30)")
+    d = _datapath_reply(ordinal_reported, "ok" if mode == "device_bad" else mode, nonce, host_ordinal, 3, stuck, 335.0,
+                        85000.0, kind="datapath_gemm")
+    d.update(ksteps=16, fill_us=37.0, verify_us=78000.0)
+    if mode == "missing":
+        d.update(error="254/256 workgroups exact (feed_bad=0 tile_bad=0)")
+    elif mode == "device_bad":
+        d.update(ok=False, records_ok=255, mfma_bad=1, stage_bad=[1, 0, 0], first_bad_wg=17, first_bad_stage=0, first_bad_word=FEED_GEMM[0],
+                 first_bad_got=FEED_GEMM[1] + 12, first_bad_want=FEED_GEMM[1], first_bad_xor=12,
+                 error=f"255/256 workgroups exact (feed_bad=1 tile_bad=0); first bad: wg 17 stage 0 word {FEED_GEMM[0]} "
+                       "xor 0x0000000c")
+    return d
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
                 "datapath_fp8": _datapath_fp8_device,
                 "datapath_f16": _datapath_f16_device,
                 "datapath_f64": _datapath_f64_device,
                 "datapath_f6f4": _datapath_f6f4_device,
-                "datapath_sparse": _datapath_sparse_device}
+                "datapath_sparse": _datapath_sparse_device,
+                "datapath_gemm": _datapath_gemm_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -375,6 +406,7 @@ _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapa
           ("datapath_f64", (_FLOAT,)),
           ("datapath_f6f4", (_FLOAT,)),
           ("datapath_sparse", (_FLOAT,)),
+          ("datapath_gemm", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -669,6 +701,7 @@ def main(argv):
                        ("--datapath-f64", "datapath_f64"),
                        ("--datapath-f6f4", "datapath_f6f4"),
                        ("--datapath-sparse", "datapath_sparse"),
+                       ("--datapath-gemm", "datapath_gemm"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
