@@ -594,6 +594,65 @@ int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, double timeout_s
 // workgroup 0's stage-`stage` data (0: A fold word, 1: B fold word, 2: D word) is flipped before the verdict.
 void mi355x_hsa_datapath_gemm_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- split-K GEMM check (partial tiles summed by L2 atomics, bit-exact) ----
+// In the checks above a workgroup writes only words no other workgroup touches.
+// Here (datapath_splitk_kernel.h) cu_count / 8 tiles of 128 x 128 are each
+// computed by 8 workgroups, one per eighth of K = 2048, on the GEMM check's
+// operands: mi355x_splitk_fill writes A, B, D = C and a zeroed ledger into device
+// memory; mi355x_mfma_datapath_splitk computes each partial through chains of
+// v_mfma_f32_16x16x32_bf16 and adds it into D with no-return, agent-scope
+// global_atomic_add_f32, and updates the tile's ledger with global_atomic_add /
+// global_atomic_xor; mi355x_splitk_drain copies D and the ledgers to host memory.
+// Every sum is exact in any arrival order, so the host checks every D word
+// exactly (datapath_splitk_verify.h). stage_bad: wrong fold words of the A feed,
+// of the B feed, wrong D words, wrong ledger words; mfma_bad = the feeds' sum,
+// tile_bad = the D words, ledger_bad = the ledger words; records_ok counts exact
+// tiles and first_bad_wg names a tile. first_bad_word: wg * 8 + wave * 2 +
+// {xor, sum} for stages 0 and 1, tile * 16384 + row * 128 + column for stage 2,
+// tile * 8 + ledger word for stage 3.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;               // tiles * splits workgroups
+  int tiles;
+  int splits;
+  int ksteps;             // k-steps of 64 a workgroup
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[4];
+  uint32_t tile_bad;
+  uint32_t ledger_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  int xccs_per_tile_min;  // the fewest distinct XCDs among one tile's contributors: reported, not judged
+  double fill_us;         // GPU time of mi355x_splitk_fill
+  double kernel_us;       // GPU time of mi355x_mfma_datapath_splitk
+  double drain_us;        // GPU time of mi355x_splitk_drain
+  double verify_us;       // host time of the verdict
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_splitk_result;
+
+int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_splitk_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later split-K check: bit `bit` of word `word`
+// (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
+void mi355x_hsa_datapath_splitk_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -538,6 +538,10 @@ const Engine::DatapathKind Engine::kDatapathGemm = {
     "datapath_gemm", "datapath gemm check", "health.datapath_gemm_check", "mi355x_dp_datapath_gemm_checks_total",
     "bf16 GEMM pipeline checks run (HBM to LDS to MFMA chains, bit-exact, on the idle GPUs)",
     "mi355x_dp_datapath_gemm_check_failures_total", "bf16 GEMM pipeline checks that did not pass"};
+const Engine::DatapathKind Engine::kDatapathSplitk = {
+    "datapath_splitk", "datapath splitk check", "health.datapath_splitk_check", "mi355x_dp_datapath_splitk_checks_total",
+    "split-K GEMM checks run (partial tiles summed by L2 atomics, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_splitk_check_failures_total", "split-K GEMM checks that did not pass"};
 
 void Engine::liveness_pass(Reasons* reasons) {
   std::map<std::string, int> ords = judged_ordinals(*reasons);
@@ -583,7 +587,8 @@ void Engine::liveness_pass(Reasons* reasons) {
       {cfg_.datapath_f64_check_every, {&kDatapathF64, &datapath_f64_}},
       {cfg_.datapath_f6f4_check_every, {&kDatapathF6F4, &datapath_f6f4_}},
       {cfg_.datapath_sparse_check_every, {&kDatapathSparse, &datapath_sparse_}},
-      {cfg_.datapath_gemm_check_every, {&kDatapathGemm, &datapath_gemm_}}};
+      {cfg_.datapath_gemm_check_every, {&kDatapathGemm, &datapath_gemm_}},
+      {cfg_.datapath_splitk_check_every, {&kDatapathSplitk, &datapath_splitk_}}};
   for (const auto& [every, check] : datapath_checks) {
     if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
@@ -594,7 +599,7 @@ void Engine::liveness_pass(Reasons* reasons) {
   std::lock_guard<std::mutex> lk(mu_);
   for (const DatapathState* st :
        {&datapath_, &datapath_i8_, &datapath_bf16_, &datapath_fp8_, &datapath_f16_, &datapath_f64_,
-        &datapath_f6f4_, &datapath_sparse_, &datapath_gemm_})
+        &datapath_f6f4_, &datapath_sparse_, &datapath_gemm_, &datapath_splitk_})
     for (const auto& [id, why] : st->failed)
       if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
@@ -1141,6 +1146,11 @@ std::map<std::string, std::string> Engine::datapath_sparse_failed() const {
 std::map<std::string, std::string> Engine::datapath_gemm_failed() const {
   std::lock_guard<std::mutex> lk(mu_);
   return datapath_gemm_.failed;
+}
+
+std::map<std::string, std::string> Engine::datapath_splitk_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_splitk_.failed;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

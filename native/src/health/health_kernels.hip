@@ -11,3 +11,4 @@
 #include "datapath_f6f4_kernel.hip"
 #include "datapath_sparse_kernel.hip"
 #include "datapath_gemm_kernel.hip"
+#include "datapath_splitk_kernel.hip"

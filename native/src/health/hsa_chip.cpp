@@ -9,7 +9,8 @@
 // mi355x_hsa_datapath_f64_check: f64 operands and accumulators;
 // mi355x_hsa_datapath_f6f4_check: fp6 / fp4 MX-scaled operands;
 // mi355x_hsa_datapath_sparse_check: the 2:4 sparse forms, v_smfmac_*;
-// mi355x_hsa_datapath_gemm_check: a bf16 GEMM out of HBM through LDS), all on the
+// mi355x_hsa_datapath_gemm_check: a bf16 GEMM out of HBM through LDS;
+// mi355x_hsa_datapath_splitk_check: split-K partials summed by L2 atomics), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -38,6 +39,7 @@
 #include "datapath_i8_verify.h"
 #include "datapath_gemm_verify.h"
 #include "datapath_sparse_verify.h"
+#include "datapath_splitk_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_json.h"
@@ -432,6 +434,7 @@ int g_dpd_corrupt[4] = {-1, 0, 0, -1};   // --corrupt-datapath-f64, likewise
 int g_dpf6_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f6f4, likewise
 int g_dpsp_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-sparse, likewise
 int g_dpgm_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-gemm, likewise
+int g_dpsk_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-splitk, likewise
 
 }  // namespace
 }  // namespace mi355x::hsa_rt
@@ -947,6 +950,85 @@ extern "C" int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, doubl
   }
   const auto t_verify = std::chrono::steady_clock::now();
   mi355x::datapath_gemm_verdict(records, tiles, grid, MI355X_DPGM_KSTEPS, out);
+  out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_splitk_corrupt(int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  g_dpsk_corrupt[0] = stage;
+  g_dpsk_corrupt[1] = word;
+  g_dpsk_corrupt[2] = bit;
+  g_dpsk_corrupt[3] = ordinal;
+}
+
+extern "C" int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, double timeout_s,
+                                                mi355x_datapath_splitk_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_splitk_result>(ordinal, nonce);
+  out->splits = MI355X_DPSK_SPLITS;
+  out->ksteps = MI355X_DPSK_KSTEPS;
+  Check<mi355x_datapath_splitk_result> c(ordinal, timeout_s, out);
+  KernelInfo ks[3];  // fill, split-K GEMM, drain
+  // the operands, D and the ledgers live in device memory; records, the drained copies and kernargs in host pools
+  if (!c.begin(true, &mi355x_datapath_splitk_result::grid, 1, "datapath_splitk",
+               {{"mi355x_splitk_fill.kd", sizeof(mi355x_datapath_splitk_args)},
+                {"mi355x_mfma_datapath_splitk.kd", sizeof(mi355x_datapath_splitk_args)},
+                {"mi355x_splitk_drain.kd", sizeof(mi355x_datapath_splitk_args)}},
+               ks))
+    return 1;
+  // a tile per 8 CUs, so that its 8 contributors are in flight together with everyone else's
+  const uint32_t tiles = std::max(1u, static_cast<uint32_t>(out->cu_count) / MI355X_DPSK_CUS_PER_TILE);
+  const uint32_t grid = tiles * MI355X_DPSK_SPLITS;
+  out->tiles = static_cast<int>(tiles);
+  out->grid = static_cast<int>(grid);
+  const size_t K = static_cast<size_t>(MI355X_DPSK_SPLITS) * MI355X_DPSK_KSTEPS * MI355X_DPGM_KSTEP;
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPSK_REC_WORDS * sizeof(uint32_t);
+  const size_t d_bytes = static_cast<size_t>(tiles) * MI355X_DPSK_TILE_WORDS * sizeof(uint32_t);
+  const size_t led_bytes = static_cast<size_t>(tiles) * MI355X_DPSK_LEDGER_WORDS * sizeof(uint32_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* out_d = c.bufs.alloc<uint32_t>(g_rt.fine, d_bytes, "alloc tiles", c.ag, "allow tiles");
+  auto* out_led = c.bufs.alloc<uint32_t>(g_rt.fine, led_bytes, "alloc ledgers", c.ag, "allow ledgers");
+  // written by mi355x_splitk_fill, whole, before the GEMM touches them, and read back by mi355x_splitk_drain: no
+  // runtime fill or copy (ROCr would open a queue)
+  auto* a = c.bufs.alloc<uint16_t>(c.ag->coarse, tiles * MI355X_DPGM_TILE * K * sizeof(uint16_t), "alloc A");
+  auto* b = c.bufs.alloc<uint16_t>(c.ag->coarse, K * MI355X_DPGM_TILE * sizeof(uint16_t), "alloc B");
+  auto* d = c.bufs.alloc<float>(c.ag->coarse, d_bytes, "alloc D");
+  auto* ledger = c.bufs.alloc<uint32_t>(c.ag->coarse, led_bytes, "alloc ledger");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_splitk_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(out_d, 0xFF, d_bytes);
+  std::memset(out_led, 0xFF, led_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->out_d = out_d;
+  kargs->out_ledger = out_led;
+  kargs->a = a;
+  kargs->b = b;
+  kargs->d = d;
+  kargs->ledger = ledger;
+  kargs->nonce = nonce;
+  kargs->tiles = tiles;
+  kargs->splits = MI355X_DPSK_SPLITS;
+  kargs->ksteps = MI355X_DPSK_KSTEPS;
+  if (!c.run(ks[0], kargs, grid, MI355X_DPSK_THREADS, "datapath splitk fill", &out->fill_us) ||
+      !c.run(ks[1], kargs, grid, MI355X_DPSK_THREADS, "datapath splitk check", &out->kernel_us) ||
+      !c.run(ks[2], kargs, tiles, MI355X_DPSK_THREADS, "datapath splitk drain", &out->drain_us))
+    return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = g_dpsk_corrupt;
+    const int words = static_cast<int>(cr[0] == 2 ? tiles * MI355X_DPSK_TILE_WORDS
+                                       : cr[0] == 3 ? tiles * MI355X_DPSK_LEDGER_WORDS : grid * 8);
+    if (cr[0] >= 0 && cr[0] < MI355X_DPSK_STAGES && cr[1] >= 0 && cr[1] < words && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      (cr[0] == 2   ? out_d[cr[1]]
+       : cr[0] == 3 ? out_led[cr[1]]
+                    : records[(cr[1] / 8) * MI355X_DPSK_REC_WORDS + dpsk_fold_slot(cr[0], cr[1] % 8)]) ^= 1u << cr[2];
+  }
+  const auto t_verify = std::chrono::steady_clock::now();
+  mi355x::datapath_splitk_verdict(records, out_d, out_led, tiles, MI355X_DPSK_SPLITS, MI355X_DPSK_KSTEPS, out);
   out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
 }

@@ -63,7 +63,8 @@ R blank_result(int ordinal, uint32_t nonce) {
                 std::is_same_v<R, mi355x_datapath_f64_result> ||
                 std::is_same_v<R, mi355x_datapath_f6f4_result> ||
                 std::is_same_v<R, mi355x_datapath_sparse_result> ||
-                std::is_same_v<R, mi355x_datapath_gemm_result>)
+                std::is_same_v<R, mi355x_datapath_gemm_result> ||
+                std::is_same_v<R, mi355x_datapath_splitk_result>)
     r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
   if constexpr (!std::is_same_v<R, mi355x_probe_result>) r.kfd_node_id = -1;  // a check that names no agent
   return r;
@@ -247,6 +248,24 @@ inline std::string datapath_gemm_json(const mi355x_datapath_gemm_result& r) {
       r.kfd_node_id, json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
 }
 
+// the split-K GEMM check's line: the GEMM check's fields with four stages (A feed, B feed, D words, ledger), the tile
+// and split counts, the drain's GPU time and the fewest XCDs that served one tile
+inline std::string datapath_splitk_json(const mi355x_datapath_splitk_result& r) {
+  return json_format(
+      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"tiles\":%d,\"splits\":%d,\"ksteps\":%d,"
+      "\"cu_count\":%d,\"num_xcc\":%d,\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u],\"tile_bad\":%u,"
+      "\"ledger_bad\":%u,\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
+      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
+      "\"xccs_per_tile_min\":%d,\"fill_us\":%.2f,\"kernel_us\":%.2f,\"drain_us\":%.2f,\"verify_us\":%.1f,\"total_us\":%.1f,"
+      "\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
+      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.tiles, r.splits, r.ksteps, r.cu_count, r.num_xcc,
+      r.records_ok, r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.tile_bad, r.ledger_bad,
+      r.first_bad_wg, r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor,
+      r.cus_covered, r.simds_covered, r.xccs_covered, r.xccs_per_tile_min, r.fill_us, r.kernel_us, r.drain_us, r.verify_us,
+      r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id, json_escape(r.pci_bus_id).c_str(),
+      json_escape(r.error).c_str());
+}
+
 // phase_us of one device: HSA build = code object, queue, buffers, dispatch;
 // HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch
 inline std::string device_json(const mi355x_probe_result& r, bool hsa_build) {
@@ -302,6 +321,7 @@ inline std::string serve_reply_json(bool tagged, unsigned long long id, const st
                     : kind == "datapath_f6f4" ? "\"datapath_f6f4\":true,"
                     : kind == "datapath_sparse" ? "\"datapath_sparse\":true,"
                     : kind == "datapath_gemm" ? "\"datapath_gemm\":true,"
+                    : kind == "datapath_splitk" ? "\"datapath_splitk\":true,"
                                               : "";
   return head + key + "\"devices\":" + devices + "}";
 }
@@ -321,7 +341,7 @@ inline std::string runtime_init_failed_json(int code, uint64_t t_start_ns, const
 }
 
 // --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16 / --datapath-f64 /
-// --datapath-f6f4 / --datapath-sparse / --datapath-gemm
+// --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk
 inline std::string oneshot_check_json(const std::string& kind, bool ok, int n, uint64_t t_start_ns,
                                       uint64_t t_runtime_ns, uint64_t t_ready_ns, const std::string& devices) {
   return json_format(

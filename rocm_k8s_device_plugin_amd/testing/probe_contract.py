@@ -5,7 +5,7 @@ The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
 (chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h,
 datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h, datapath_f6f4_verify.h,
-datapath_sparse_verify.h, datapath_gemm_verify.h) says the same of the
+datapath_sparse_verify.h, datapath_gemm_verify.h, datapath_splitk_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -29,6 +29,7 @@ from . import datapath_f6f4_reference as dpf6
 from . import datapath_i8_reference as dpi8
 from . import datapath_sparse_reference as dpsp
 from . import datapath_gemm_reference as dpgm
+from . import datapath_splitk_reference as dpsk
 from . import datapath_reference as dp
 from . import kernel_reference as ref
 
@@ -56,11 +57,11 @@ DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad"
 KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
         "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS, "datapath_f16": DATAPATH_KEYS,
         "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS, "datapath_sparse": DATAPATH_KEYS,
-        "datapath_gemm": DATAPATH_KEYS}
+        "datapath_gemm": DATAPATH_KEYS, "datapath_splitk": DATAPATH_KEYS + ("tiles", "splits", "ledger_bad")}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
          "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES,
          "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES, "datapath_sparse": DATAPATH_MODES,
-         "datapath_gemm": DATAPATH_MODES}
+         "datapath_gemm": DATAPATH_MODES, "datapath_splitk": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -264,6 +265,30 @@ def datapath_gemm_replies(build_dir) -> list:
     return out
 
 
+def datapath_splitk_replies(build_dir) -> list:
+    """As datapath_gemm_replies for the split-K check at the production sizes (GRID / 8 tiles, 8 splits of 4 k-steps).
+    stuck_bit: bit 30 of every D word of row 0 of tile WG; missing: workgroups WG and WG + 1 (both of tile WG // 8)
+    wrote no record; device_bad: workgroup WG's first A fold sum is off by 12."""
+    cli = contract_cli.datapath_splitk_cli(build_dir)
+    tiles, sizes = GRID // dpsk.CUS_PER_TILE, (GRID // dpsk.CUS_PER_TILE, dpsk.SPLITS, dpsk.KSTEPS, NONCE)
+    healthy = np.frombuffer(contract_cli.datapath_splitk_image(cli, *sizes), dtype="<u4")
+    out = []
+    for mode in MODES["datapath_splitk"]:
+        recs, d, led = (x.copy() for x in np.split(healthy, [GRID * dpsk.REC_WORDS, GRID * dpsk.REC_WORDS + tiles * dpsk.TILE_WORDS]))
+        if mode == "stuck_bit":
+            d.reshape(tiles, dpsk.TILE_WORDS)[WG, :dpsk.TILE] &= np.uint32(~(1 << BIT) & 0xFFFFFFFF)
+        elif mode == "missing":
+            recs.reshape(GRID, dpsk.REC_WORDS)[WG:WG + 2, :] = 0
+        elif mode == "device_bad":
+            recs.reshape(GRID, dpsk.REC_WORDS)[WG, dpsk.fold_slot(0, 1)] += 12
+        else:
+            assert mode == "ok", mode
+        r = contract_cli.datapath_splitk_verdict(cli, dpsk.image_bytes(recs, d, led), *sizes, build_dir)
+        assert r.returncode == 0, r.stderr
+        out.append(json.loads(r.stdout))
+    return out
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -293,6 +318,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = datapath_sparse_replies(build_dir)
     elif kind == "datapath_gemm":
         out = datapath_gemm_replies(build_dir)
+    elif kind == "datapath_splitk":
+        out = datapath_splitk_replies(build_dir)
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:

@@ -25,6 +25,11 @@ REQUESTS.json is a list of requests, run in order:
         "inject" may also be {"kind": "lds", "wg": w, "step": s, "index": LDS dword of the step's buffer, "mask": m}
         or {"kind": "hbm", "wg": w, "index": row * K + k of A, "mask": m})
 
+    {"id": ..., "kernel": "datapath_splitk", "nonce": n, "tiles": t, "splits": s, "ksteps": k[, "launch_grid": ...]}
+        (mi355x_splitk_fill, mi355x_mfma_datapath_splitk, then mi355x_splitk_drain, on the same arguments and
+        workgroups, t * s or launch_grid; with the inject build "inject" is {"kind": "atomic" or "drop", "wg": w,
+        "wave": v, "lane": l, "index": accumulator word 0..63, "mask": m})
+
 A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64, datapath_f6f4 or datapath_sparse request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
 the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h /
@@ -229,6 +234,21 @@ DATAPATH_GEMM_INJECT_ARG_STRUCTS = {"mi355x_datapath_gemm_args": DatapathGemmInj
 DATAPATH_GEMM_WG_WORDS = 128 * 128                   # the whole D tile of one workgroup
 DATAPATH_GEMM_REC_WORDS = 32
 DATAPATH_GEMM_INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2, "hbm": 3}   # MI355X_DPGM_INJECT_*
+
+
+class DatapathSplitkArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("out_d", _ptr), ("out_ledger", _ptr), ("a", _ptr), ("b", _ptr), ("d", _ptr),
+                ("ledger", _ptr), ("nonce", _u32), ("tiles", _u32), ("splits", _u32), ("ksteps", _u32)]
+
+
+class DatapathSplitkInjectArgs(ctypes.Structure):
+    _fields_ = DatapathSplitkArgs._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_splitk_kernel.h; the three kernels of the check take the one struct
+DATAPATH_SPLITK_ARG_STRUCTS = {"mi355x_datapath_splitk_args": DatapathSplitkArgs}
+DATAPATH_SPLITK_INJECT_ARG_STRUCTS = {"mi355x_datapath_splitk_args": DatapathSplitkInjectArgs}
+DATAPATH_SPLITK_INJECT_KINDS = {"none": 0, "atomic": 1, "drop": 2}   # MI355X_DPSK_INJECT_*
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -241,6 +261,9 @@ def inject_words(req: dict) -> tuple:
     if req["kernel"] == "datapath_gemm":                 # the wave field carries the step of an lds injection
         return (DATAPATH_GEMM_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj.get("wave", inj.get("step", 0))),
                 int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
+    if req["kernel"] == "datapath_splitk":
+        return (DATAPATH_SPLITK_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj["wave"]), int(inj["lane"]),
+                int(inj["index"]), int(inj.get("mask", 0)) & 0xFFFFFFFF)
     kind = INJECT_KINDS[inj["kind"]]
     if req["kernel"] in ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                          "datapath_f16", "datapath_f64", "datapath_f6f4", "datapath_sparse") and inj["kind"] == "lds":
@@ -255,7 +278,7 @@ def code_object_of(req: dict) -> str:
         raise ValueError(f"unknown code object {which!r}")
     if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                                                    "datapath_f16", "datapath_f64", "datapath_f6f4",
-                                                   "datapath_sparse", "datapath_gemm"):
+                                                   "datapath_sparse", "datapath_gemm", "datapath_splitk"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -273,9 +296,11 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "datapath_f64": ("mi355x_mfma_datapath_f64", 256),
            "datapath_f6f4": ("mi355x_mfma_datapath_f6f4", 256),
            "datapath_sparse": ("mi355x_mfma_datapath_sparse", 256),
-           "datapath_gemm": ("mi355x_mfma_datapath_gemm", 256)}
-# kernel -> (symbol, lanes) of a kernel launched before it, on the same arguments and workgroups
-FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256)}
+           "datapath_gemm": ("mi355x_mfma_datapath_gemm", 256),
+           "datapath_splitk": ("mi355x_mfma_datapath_splitk", 256)}
+# kernel -> (symbol, lanes) of a kernel launched before it (FIRST) or after it (LAST), on the same arguments and workgroups
+FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256), "datapath_splitk": ("mi355x_splitk_fill", 256)}
+LAST = {"datapath_splitk": ("mi355x_splitk_drain", 256)}
 
 _H2D, _D2H = 1, 2
 _LAUNCH_PARAM_BUFFER_POINTER, _LAUNCH_PARAM_BUFFER_SIZE, _LAUNCH_PARAM_END = 1, 2, 3
@@ -486,6 +511,25 @@ def plan(req: dict, base_dir: Path):
         if wgs < g:
             raise ValueError("launch_grid below grid")
         return bufs, lambda p: DatapathGemmArgs(p["records"], p["tiles"], p["a"], p["b"], req["nonce"], g, ksteps, 0), wgs
+    if k == "datapath_splitk":
+        t, sp, ksteps = int(req["tiles"]), int(req["splits"]), int(req["ksteps"])
+        if t < 1 or sp < 1 or ksteps < 1 or sp * ksteps > 32:
+            raise ValueError("tiles, splits, ksteps: splits * ksteps outside 1..32")   # the buffers are sized by them
+        K = sp * ksteps * 64
+        bufs = [("records", np.uint32, _filled(t * sp * 32 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(t * 128 * 128 * 4, OUT_PREFILL)),          # the drain's copy of D
+                ("out_ledger", np.uint32, _filled(t * 8 * 4, OUT_PREFILL)),
+                ("a", np.uint16, _filled(t * 128 * K * 2, OUT_PREFILL)),
+                ("b", np.uint16, _filled(K * 128 * 2, OUT_PREFILL)),
+                ("d", np.uint32, _filled(t * 128 * 128 * 4, OUT_PREFILL)),
+                ("ledger", np.uint32, _filled(t * 8 * 4, OUT_PREFILL))]
+        inject = code_object_of(req) == "inject"
+        wgs = t * sp if inject else int(req.get("launch_grid", t * sp))
+        if wgs < t * sp:
+            raise ValueError("launch_grid below tiles * splits")
+        cls, tail = (DatapathSplitkInjectArgs, inject_words(req)) if inject else (DatapathSplitkArgs, ())
+        return bufs, lambda p: cls(p["records"], p["tiles"], p["out_ledger"], p["a"], p["b"], p["d"], p["ledger"],
+                                   req["nonce"], t, sp, ksteps, *tail), wgs
     raise ValueError(f"unknown kernel {k!r}")
 
 
@@ -503,6 +547,9 @@ def run_request(hip: Hip, functions: dict, req: dict, base_dir: Path, outdir: Pa
         first, first_lanes = FIRST[req["kernel"]]
         hip.call("hipModuleLaunchKernel", functions[first], wgs, 1, 1, first_lanes, 1, 1, 0, None, None, extra)
     hip.call("hipModuleLaunchKernel", functions[symbol], wgs, 1, 1, lanes, 1, 1, 0, None, None, extra)
+    if req["kernel"] in LAST:
+        last, last_lanes = LAST[req["kernel"]]
+        hip.call("hipModuleLaunchKernel", functions[last], wgs, 1, 1, last_lanes, 1, 1, 0, None, None, extra)
     hip.call("hipDeviceSynchronize")
     launch_us = (time.perf_counter_ns() - t0) / 1e3
     for b in bufs:
@@ -519,7 +566,7 @@ def load_functions(hip: Hip, path) -> dict:
     module = ctypes.c_void_p()
     hip.call("hipModuleLoad", ctypes.byref(module), str(path).encode())
     functions = {}
-    for symbol, _ in list(KERNELS.values()) + list(FIRST.values()):
+    for symbol, _ in list(KERNELS.values()) + list(FIRST.values()) + list(LAST.values()):
         f = ctypes.c_void_p()
         hip.call("hipModuleGetFunction", ctypes.byref(f), module, symbol.encode())
         functions[symbol] = f

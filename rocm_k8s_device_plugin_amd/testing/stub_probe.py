@@ -47,6 +47,8 @@ Sparse (2:4) MFMA datapath-check replies ("datapath_sparse" requests /
 --datapath-sparse) follow the "datapath_sparse" map and append "datapath_sparse:<host ordinal>".
 bf16 GEMM pipeline-check replies ("datapath_gemm" requests /
 --datapath-gemm) follow the "datapath_gemm" map and append "datapath_gemm:<host ordinal>".
+Split-K GEMM check replies ("datapath_splitk" requests /
+--datapath-splitk) follow the "datapath_splitk" map and append "datapath_splitk:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -102,7 +104,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
 
 
 DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16", "datapath_f64",
-                  "datapath_f6f4", "datapath_sparse", "datapath_gemm")
+                  "datapath_f6f4", "datapath_sparse", "datapath_gemm", "datapath_splitk")
 
 
 def _log_check(kind, host_ordinal):
@@ -323,6 +325,39 @@ def _datapath_gemm_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return d
 
 
+# the shipped verdict's figures for the splitk kind's faults at nonce 0x5EED142F (testing/probe_contract.py builds them):
+# stuck_bit = bit 30 of the 128 D words of row 0 of tile 17 (its first word's healthy value), device_bad = fold word 1
+# of the A feed of workgroup 17 (tile 2) off by 12 (its healthy value)
+STUCK_SPLITK = (128, 17 * 16384, 1435249408)
+FEED_SPLITK = (17 * 8 + 1, 536350134)
+
+
+def _datapath_splitk_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """Split-K GEMM check reply (kind "datapath_splitk"; stages: A feed, B feed, D words, ledger); the modes of
+    _datapath_device, from the control file's "datapath_splitk" map. records_ok counts tiles."""
+    stuck = dict(records_ok=31, tile_bad=STUCK_SPLITK[0], stage_bad=[0, 0, STUCK_SPLITK[0], 0], first_bad_wg=17,
+                 first_bad_stage=2, first_bad_word=STUCK_SPLITK[1], first_bad_got=STUCK_SPLITK[2] ^ 0x40000000,
+                 first_bad_want=STUCK_SPLITK[2], first_bad_xor=0x40000000,
+                 error=f"31/32 tiles exact (feed_bad=0 tile_bad={STUCK_SPLITK[0]} ledger_bad=0); first bad: tile 17 stage 2 "
+                       f"word {STUCK_SPLITK[1]} xor 0x40000000 (bit 30)")
+    d = _datapath_reply(ordinal_reported, "ok" if mode in ("device_bad", "missing") else mode, nonce, host_ordinal, 4, stuck,
+                        60.0, 25000.0, kind="datapath_splitk")
+    d.update(tiles=32, splits=8, ksteps=4, ledger_bad=0, xccs_per_tile_min=8, fill_us=30.0, drain_us=40.0, verify_us=20000.0)
+    if mode != "stuck_bit":
+        d.update(records_ok=32)
+    if mode == "missing":
+        d.update(ok=False, records_ok=31, cus_covered=254, simds_covered=1016,
+                 error="31/32 tiles exact (feed_bad=0 tile_bad=0 ledger_bad=0)")
+    elif mode == "device_bad":
+        got = FEED_SPLITK[1] + 12
+        d.update(ok=False, records_ok=31, mfma_bad=1, stage_bad=[1, 0, 0, 0], first_bad_wg=2, first_bad_stage=0,
+                 first_bad_word=FEED_SPLITK[0], first_bad_got=got, first_bad_want=FEED_SPLITK[1],
+                 first_bad_xor=got ^ FEED_SPLITK[1],
+                 error=f"31/32 tiles exact (feed_bad=1 tile_bad=0 ledger_bad=0); first bad: tile 2 stage 0 word "
+                       f"{FEED_SPLITK[0]} xor 0x{got ^ FEED_SPLITK[1]:08x}")
+    return d
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
                 "datapath_fp8": _datapath_fp8_device,
@@ -330,7 +365,8 @@ CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datap
                 "datapath_f64": _datapath_f64_device,
                 "datapath_f6f4": _datapath_f6f4_device,
                 "datapath_sparse": _datapath_sparse_device,
-                "datapath_gemm": _datapath_gemm_device}
+                "datapath_gemm": _datapath_gemm_device,
+                "datapath_splitk": _datapath_splitk_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -407,6 +443,7 @@ _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapa
           ("datapath_f6f4", (_FLOAT,)),
           ("datapath_sparse", (_FLOAT,)),
           ("datapath_gemm", (_FLOAT,)),
+          ("datapath_splitk", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -702,6 +739,7 @@ def main(argv):
                        ("--datapath-f6f4", "datapath_f6f4"),
                        ("--datapath-sparse", "datapath_sparse"),
                        ("--datapath-gemm", "datapath_gemm"),
+                       ("--datapath-splitk", "datapath_splitk"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
