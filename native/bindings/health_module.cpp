@@ -64,6 +64,7 @@ class PyHealthEngine {
     i("datapath_sparse_check_every", &c.datapath_sparse_check_every);
     i("datapath_gemm_check_every", &c.datapath_gemm_check_every);
     i("datapath_splitk_check_every", &c.datapath_splitk_check_every);
+    i("datapath_attn_check_every", &c.datapath_attn_check_every);
     d("perf_min_hbm_read_gbps", &c.perf_min_hbm_read_gbps);
     d("perf_min_hbm_write_gbps", &c.perf_min_hbm_write_gbps);
     d("perf_min_mfma_tflops", &c.perf_min_mfma_tflops);
@@ -131,11 +132,13 @@ class PyHealthEngine {
     d["datapath_sparse_checks"] = eng_->datapath_sparse_checks();
     d["datapath_gemm_checks"] = eng_->datapath_gemm_checks();
     d["datapath_splitk_checks"] = eng_->datapath_splitk_checks();
+    d["datapath_attn_checks"] = eng_->datapath_attn_checks();
     d["datapath_f64_failures"] = eng_->datapath_f64_failures();
     d["datapath_f6f4_failures"] = eng_->datapath_f6f4_failures();
     d["datapath_sparse_failures"] = eng_->datapath_sparse_failures();
     d["datapath_gemm_failures"] = eng_->datapath_gemm_failures();
     d["datapath_splitk_failures"] = eng_->datapath_splitk_failures();
+    d["datapath_attn_failures"] = eng_->datapath_attn_failures();
     if (auto* p = eng_->prober()) {
       d["server_starts"] = p->server_starts.load();
       d["server_restarts"] = p->server_restarts.load();

@@ -48,7 +48,7 @@ py::dict to_dict(const mi355x_probe_result& r) {
 }  // namespace
 
 // mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result / _f16_result / _f64_result /
-// _f6f4_result / _sparse_result / _gemm_result / _splitk_result (the same
+// _f6f4_result / _sparse_result / _gemm_result / _splitk_result / _attn_result (the same
 // fields; stage_bad differs in length)
 template <typename R>
 py::dict datapath_dict(const R& r) {
@@ -283,6 +283,24 @@ PYBIND11_MODULE(_hip, m) {
         d["xccs_per_tile_min"] = r.xccs_per_tile_min;
         d["fill_us"] = r.fill_us;
         d["drain_us"] = r.drain_us;
+        d["verify_us"] = r.verify_us;
+        return d;
+      },
+      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+  m.def(
+      "hsa_datapath_attn_check",
+      [](int ordinal, uint32_t nonce, double timeout_s) {
+        mi355x_datapath_attn_result r;
+        {
+          py::gil_scoped_release nogil;
+          mi355x_hsa_datapath_attn_check(ordinal, nonce, timeout_s, &r);
+        }
+        py::dict d = datapath_dict(r);
+        d["heads"] = r.heads;
+        d["qblocks"] = r.qblocks;
+        d["kblocks"] = r.kblocks;
+        d["exp_inexact"] = r.exp_inexact;
+        d["fill_us"] = r.fill_us;
         d["verify_us"] = r.verify_us;
         return d;
       },

@@ -653,6 +653,61 @@ int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, double timeout
 // (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
 void mi355x_hsa_datapath_splitk_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- fused attention check (MFMA, online softmax, MFMA; bit-exact) ----
+// The checks above cover what a tenant's GEMM does. Here (datapath_attn_kernel.h)
+// cu_count / 4 heads of 256 keys and 512 queries, d = 64, go through a
+// flash-attention loop: mi355x_attn_fill writes Q, K and V into device memory;
+// mi355x_mfma_datapath_attn computes S^T = K . Q^T by v_mfma_f32_32x32x16_bf16,
+// the running row max (v_max3_f32, v_permlane32_swap), P = v_exp_f32(S - m) packed
+// by v_cvt_pk_bf16_f32 and moved across the half-waves by v_permlane32_swap into
+// the B operand of O^T += V^T . P^T, with O and l rescaled by v_ldexp_f32 between
+// the MFMAs. Every m, l and O word is exact in any order, so the host checks
+// every one (datapath_attn_verify.h). stage_bad: wrong fold words of the K feed,
+// of the V feed, wrong m / l words, wrong O words; mfma_bad = the feeds' sum,
+// tile_bad = the m / l and O words; records_ok counts exact workgroups.
+// first_bad_word: wg * 8 + wave * 2 + {xor, sum} for stages 0 and 1,
+// wg * 256 + query * 2 + {m, l} for stage 2, wg * 8192 + query * 64 + d for stage 3.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;               // heads * qblocks workgroups
+  int heads;
+  int qblocks;            // blocks of 128 queries a head
+  int kblocks;            // blocks of 64 keys a head
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[4];
+  uint32_t tile_bad;
+  uint32_t exp_inexact;   // v_exp_f32 results that were not exact powers of two: reported, not judged
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double fill_us;         // GPU time of mi355x_attn_fill
+  double kernel_us;       // GPU time of mi355x_mfma_datapath_attn
+  double verify_us;       // host time of the verdict
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_attn_result;
+
+int mi355x_hsa_datapath_attn_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_attn_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later attention check: bit `bit` of word `word`
+// (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
+void mi355x_hsa_datapath_attn_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -542,6 +542,10 @@ const Engine::DatapathKind Engine::kDatapathSplitk = {
     "datapath_splitk", "datapath splitk check", "health.datapath_splitk_check", "mi355x_dp_datapath_splitk_checks_total",
     "split-K GEMM checks run (partial tiles summed by L2 atomics, bit-exact, on the idle GPUs)",
     "mi355x_dp_datapath_splitk_check_failures_total", "split-K GEMM checks that did not pass"};
+const Engine::DatapathKind Engine::kDatapathAttn = {
+    "datapath_attn", "datapath attn check", "health.datapath_attn_check", "mi355x_dp_datapath_attn_checks_total",
+    "fused attention checks run (MFMA, online softmax, MFMA, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_attn_check_failures_total", "fused attention checks that did not pass"};
 
 void Engine::liveness_pass(Reasons* reasons) {
   std::map<std::string, int> ords = judged_ordinals(*reasons);
@@ -588,7 +592,8 @@ void Engine::liveness_pass(Reasons* reasons) {
       {cfg_.datapath_f6f4_check_every, {&kDatapathF6F4, &datapath_f6f4_}},
       {cfg_.datapath_sparse_check_every, {&kDatapathSparse, &datapath_sparse_}},
       {cfg_.datapath_gemm_check_every, {&kDatapathGemm, &datapath_gemm_}},
-      {cfg_.datapath_splitk_check_every, {&kDatapathSplitk, &datapath_splitk_}}};
+      {cfg_.datapath_splitk_check_every, {&kDatapathSplitk, &datapath_splitk_}},
+      {cfg_.datapath_attn_check_every, {&kDatapathAttn, &datapath_attn_}}};
   for (const auto& [every, check] : datapath_checks) {
     if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
@@ -599,7 +604,7 @@ void Engine::liveness_pass(Reasons* reasons) {
   std::lock_guard<std::mutex> lk(mu_);
   for (const DatapathState* st :
        {&datapath_, &datapath_i8_, &datapath_bf16_, &datapath_fp8_, &datapath_f16_, &datapath_f64_,
-        &datapath_f6f4_, &datapath_sparse_, &datapath_gemm_, &datapath_splitk_})
+        &datapath_f6f4_, &datapath_sparse_, &datapath_gemm_, &datapath_splitk_, &datapath_attn_})
     for (const auto& [id, why] : st->failed)
       if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
@@ -1151,6 +1156,11 @@ std::map<std::string, std::string> Engine::datapath_gemm_failed() const {
 std::map<std::string, std::string> Engine::datapath_splitk_failed() const {
   std::lock_guard<std::mutex> lk(mu_);
   return datapath_splitk_.failed;
+}
+
+std::map<std::string, std::string> Engine::datapath_attn_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_attn_.failed;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

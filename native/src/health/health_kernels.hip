@@ -12,3 +12,4 @@
 #include "datapath_sparse_kernel.hip"
 #include "datapath_gemm_kernel.hip"
 #include "datapath_splitk_kernel.hip"
+#include "datapath_attn_kernel.hip"

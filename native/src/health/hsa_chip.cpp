@@ -10,7 +10,8 @@
 // mi355x_hsa_datapath_f6f4_check: fp6 / fp4 MX-scaled operands;
 // mi355x_hsa_datapath_sparse_check: the 2:4 sparse forms, v_smfmac_*;
 // mi355x_hsa_datapath_gemm_check: a bf16 GEMM out of HBM through LDS;
-// mi355x_hsa_datapath_splitk_check: split-K partials summed by L2 atomics), all on the
+// mi355x_hsa_datapath_splitk_check: split-K partials summed by L2 atomics;
+// mi355x_hsa_datapath_attn_check: a flash-attention loop, MFMA to softmax to MFMA), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -40,6 +41,7 @@
 #include "datapath_gemm_verify.h"
 #include "datapath_sparse_verify.h"
 #include "datapath_splitk_verify.h"
+#include "datapath_attn_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_json.h"
@@ -435,6 +437,7 @@ int g_dpf6_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f6f4, likewise
 int g_dpsp_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-sparse, likewise
 int g_dpgm_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-gemm, likewise
 int g_dpsk_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-splitk, likewise
+int g_dpat_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-attn, likewise
 
 }  // namespace
 }  // namespace mi355x::hsa_rt
@@ -1029,6 +1032,82 @@ extern "C" int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, dou
   }
   const auto t_verify = std::chrono::steady_clock::now();
   mi355x::datapath_splitk_verdict(records, out_d, out_led, tiles, MI355X_DPSK_SPLITS, MI355X_DPSK_KSTEPS, out);
+  out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_attn_corrupt(int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  g_dpat_corrupt[0] = stage;
+  g_dpat_corrupt[1] = word;
+  g_dpat_corrupt[2] = bit;
+  g_dpat_corrupt[3] = ordinal;
+}
+
+extern "C" int mi355x_hsa_datapath_attn_check(int ordinal, uint32_t nonce, double timeout_s,
+                                              mi355x_datapath_attn_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_attn_result>(ordinal, nonce);
+  out->qblocks = MI355X_DPAT_QBLOCKS;
+  out->kblocks = MI355X_DPAT_KBLOCKS;
+  Check<mi355x_datapath_attn_result> c(ordinal, timeout_s, out);
+  KernelInfo ks[2];  // fill, attention
+  // the operands live in device memory; records, m / l, O and kernargs in host pools
+  if (!c.begin(true, &mi355x_datapath_attn_result::grid, 1, "datapath_attn",
+               {{"mi355x_attn_fill.kd", sizeof(mi355x_datapath_attn_args)},
+                {"mi355x_mfma_datapath_attn.kd", sizeof(mi355x_datapath_attn_args)}},
+               ks))
+    return 1;
+  // a head per 4 CUs: its 4 workgroups, one a CU, read the same K and V through L2
+  const uint32_t heads = std::max(1u, static_cast<uint32_t>(out->cu_count) / MI355X_DPAT_CUS_PER_HEAD);
+  const uint32_t grid = heads * MI355X_DPAT_QBLOCKS;
+  out->heads = static_cast<int>(heads);
+  out->grid = static_cast<int>(grid);
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPAT_REC_WORDS * sizeof(uint32_t);
+  const size_t ml_bytes = static_cast<size_t>(grid) * MI355X_DPAT_ML_WORDS * sizeof(uint32_t);
+  const size_t o_bytes = static_cast<size_t>(grid) * MI355X_DPAT_O_WORDS * sizeof(uint32_t);
+  const size_t q_bytes = static_cast<size_t>(grid) * MI355X_DPAT_QBLOCK * MI355X_DPAT_D * sizeof(uint16_t);
+  const size_t kv_bytes =
+      static_cast<size_t>(heads) * MI355X_DPAT_KBLOCKS * MI355X_DPAT_KBLOCK * MI355X_DPAT_D * sizeof(uint16_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* ml = c.bufs.alloc<uint32_t>(g_rt.fine, ml_bytes, "alloc m / l", c.ag, "allow m / l");
+  auto* o = c.bufs.alloc<uint32_t>(g_rt.fine, o_bytes, "alloc O", c.ag, "allow O");
+  // written by mi355x_attn_fill, whole, before the attention kernel reads them: no runtime fill (ROCr would open a queue)
+  auto* q = c.bufs.alloc<uint16_t>(c.ag->coarse, q_bytes, "alloc Q");
+  auto* k = c.bufs.alloc<uint16_t>(c.ag->coarse, kv_bytes, "alloc K");
+  auto* v = c.bufs.alloc<uint16_t>(c.ag->coarse, kv_bytes, "alloc V");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_attn_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(ml, 0xFF, ml_bytes);
+  std::memset(o, 0xFF, o_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->ml = ml;
+  kargs->o = o;
+  kargs->q = q;
+  kargs->k = k;
+  kargs->v = v;
+  kargs->nonce = nonce;
+  kargs->heads = heads;
+  kargs->qblocks = MI355X_DPAT_QBLOCKS;
+  kargs->kblocks = MI355X_DPAT_KBLOCKS;
+  if (!c.run(ks[0], kargs, grid, MI355X_DPAT_THREADS, "datapath attn fill", &out->fill_us) ||
+      !c.run(ks[1], kargs, grid, MI355X_DPAT_THREADS, "datapath attn check", &out->kernel_us))
+    return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = g_dpat_corrupt;
+    const int words = static_cast<int>(cr[0] == 2 ? grid * MI355X_DPAT_ML_WORDS
+                                       : cr[0] == 3 ? grid * MI355X_DPAT_O_WORDS : grid * 8);
+    if (cr[0] >= 0 && cr[0] < MI355X_DPAT_STAGES && cr[1] >= 0 && cr[1] < words && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      (cr[0] == 2   ? ml[cr[1]]
+       : cr[0] == 3 ? o[cr[1]]
+                    : records[(cr[1] / 8) * MI355X_DPAT_REC_WORDS + dpat_fold_slot(cr[0], cr[1] % 8)]) ^= 1u << cr[2];
+  }
+  const auto t_verify = std::chrono::steady_clock::now();
+  mi355x::datapath_attn_verdict(records, ml, o, heads, MI355X_DPAT_QBLOCKS, MI355X_DPAT_KBLOCKS, out);
   out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
 }

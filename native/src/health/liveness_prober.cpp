@@ -453,6 +453,7 @@ std::map<int, ProbeOutcome> LivenessProber::spawn_all(const std::vector<int>& or
       if (kind == "datapath_sparse") argv.push_back("--datapath-sparse");
       if (kind == "datapath_gemm") argv.push_back("--datapath-gemm");
       if (kind == "datapath_splitk") argv.push_back("--datapath-splitk");
+      if (kind == "datapath_attn") argv.push_back("--datapath-attn");
       if (kind == "perf")
         for (const std::string& a : {std::string("--perf"), std::string("--perf-mib"), std::to_string(cfg_.perf_mib),
                                      std::string("--perf-iters"), std::to_string(cfg_.perf_iters)})
@@ -684,7 +685,7 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
   else if (kind == "datapath" || kind == "datapath_i8" || kind == "datapath_bf16" ||
            kind == "datapath_fp8" || kind == "datapath_f16" || kind == "datapath_f64" ||
            kind == "datapath_f6f4" || kind == "datapath_sparse" || kind == "datapath_gemm" ||
-           kind == "datapath_splitk")
+           kind == "datapath_splitk" || kind == "datapath_attn")
     std::snprintf(head, sizeof(head), "%s %.3f", kind.c_str(), top);
   else
     std::snprintf(head, sizeof(head), "%s %d %.3f", kind.c_str(), cfg_.iters, top);

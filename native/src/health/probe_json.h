@@ -64,7 +64,8 @@ R blank_result(int ordinal, uint32_t nonce) {
                 std::is_same_v<R, mi355x_datapath_f6f4_result> ||
                 std::is_same_v<R, mi355x_datapath_sparse_result> ||
                 std::is_same_v<R, mi355x_datapath_gemm_result> ||
-                std::is_same_v<R, mi355x_datapath_splitk_result>)
+                std::is_same_v<R, mi355x_datapath_splitk_result> ||
+                std::is_same_v<R, mi355x_datapath_attn_result>)
     r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
   if constexpr (!std::is_same_v<R, mi355x_probe_result>) r.kfd_node_id = -1;  // a check that names no agent
   return r;
@@ -266,6 +267,23 @@ inline std::string datapath_splitk_json(const mi355x_datapath_splitk_result& r) 
       json_escape(r.error).c_str());
 }
 
+// the fused attention check's line: the GEMM check's fields with four stages (K feed, V feed, m / l words, O words), the
+// head and block counts, the fill's GPU time and the count of inexact v_exp_f32 results
+inline std::string datapath_attn_json(const mi355x_datapath_attn_result& r) {
+  return json_format(
+      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"heads\":%d,\"qblocks\":%d,\"kblocks\":%d,"
+      "\"cu_count\":%d,\"num_xcc\":%d,\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u],\"tile_bad\":%u,"
+      "\"exp_inexact\":%u,\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
+      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
+      "\"fill_us\":%.2f,\"kernel_us\":%.2f,\"verify_us\":%.1f,\"total_us\":%.1f,"
+      "\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
+      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.heads, r.qblocks, r.kblocks, r.cu_count, r.num_xcc,
+      r.records_ok, r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.tile_bad, r.exp_inexact,
+      r.first_bad_wg, r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor,
+      r.cus_covered, r.simds_covered, r.xccs_covered, r.fill_us, r.kernel_us, r.verify_us, r.total_us, r.in_flight_s,
+      r.kept_queue ? "true" : "false", r.kfd_node_id, json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
+}
+
 // phase_us of one device: HSA build = code object, queue, buffers, dispatch;
 // HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch
 inline std::string device_json(const mi355x_probe_result& r, bool hsa_build) {
@@ -322,6 +340,7 @@ inline std::string serve_reply_json(bool tagged, unsigned long long id, const st
                     : kind == "datapath_sparse" ? "\"datapath_sparse\":true,"
                     : kind == "datapath_gemm" ? "\"datapath_gemm\":true,"
                     : kind == "datapath_splitk" ? "\"datapath_splitk\":true,"
+                    : kind == "datapath_attn" ? "\"datapath_attn\":true,"
                                               : "";
   return head + key + "\"devices\":" + devices + "}";
 }
@@ -341,7 +360,7 @@ inline std::string runtime_init_failed_json(int code, uint64_t t_start_ns, const
 }
 
 // --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16 / --datapath-f64 /
-// --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk
+// --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk / --datapath-attn
 inline std::string oneshot_check_json(const std::string& kind, bool ok, int n, uint64_t t_start_ns,
                                       uint64_t t_runtime_ns, uint64_t t_ready_ns, const std::string& devices) {
   return json_format(

@@ -15,6 +15,7 @@
 //   mi355x-liveness-probe --datapath-sparse [--devices ..] (the 2:4 sparse forms, see mi355x_mfma_datapath_sparse)
 //   mi355x-liveness-probe --datapath-gemm [--devices ..] (a bf16 GEMM out of HBM through LDS, see mi355x_mfma_datapath_gemm)
 //   mi355x-liveness-probe --datapath-splitk [--devices ..] (split-K partials summed by L2 atomics, see mi355x_mfma_datapath_splitk)
+//   mi355x-liveness-probe --datapath-attn [--devices ..] (a flash-attention loop, see mi355x_mfma_datapath_attn)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
@@ -29,6 +30,8 @@
 //   --corrupt-datapath-gemm S:W:B[@O]: the same for the GEMM pipeline check (S 0 = A fold, 1 = B fold, 2 = D word)
 //   --corrupt-datapath-splitk S:W:B[@O]: the same for the split-K check (S 0 = A fold, 1 = B fold, 2 = D word,
 //       3 = ledger word; W numbered over all tiles, as first_bad_word)
+//   --corrupt-datapath-attn S:W:B[@O]: the same for the attention check (S 0 = K fold, 1 = V fold, 2 = m / l word,
+//       3 = O word; W numbered over all workgroups, as first_bad_word)
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -100,6 +103,7 @@ using mi355x::datapath_f6f4_json;
 using mi355x::datapath_sparse_json;
 using mi355x::datapath_gemm_json;
 using mi355x::datapath_splitk_json;
+using mi355x::datapath_attn_json;
 using mi355x::datapath_i8_json;
 using mi355x::datapath_json;
 using mi355x::json_escape;
@@ -192,6 +196,12 @@ int datapath_splitk_check(int o, uint32_t nonce, double timeout_s, mi355x_datapa
 void datapath_splitk_corrupt(int stage, int word, int bit, int ordinal) {
   mi355x_hsa_datapath_splitk_corrupt(stage, word, bit, ordinal);
 }
+int datapath_attn_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_attn_result* r) {
+  return mi355x_hsa_datapath_attn_check(o, nonce, timeout_s, r);
+}
+void datapath_attn_corrupt(int stage, int word, int bit, int ordinal) {
+  mi355x_hsa_datapath_attn_corrupt(stage, word, bit, ordinal);
+}
 void init_phases(double out[5]) { mi355x_hsa_init_phases(out); }
 void defer_teardown() { mi355x_hsa_probe_defer_release(1); }
 void teardown() { mi355x_hsa_probe_release(); }
@@ -264,6 +274,10 @@ int datapath_gemm_check(int o, uint32_t nonce, double, mi355x_datapath_gemm_resu
 void datapath_splitk_corrupt(int, int, int, int) {}
 int datapath_splitk_check(int o, uint32_t nonce, double, mi355x_datapath_splitk_result* r) {
   return needs_hsa_build("--datapath-splitk", blank_result<mi355x_datapath_splitk_result>(o, nonce), r);
+}
+void datapath_attn_corrupt(int, int, int, int) {}
+int datapath_attn_check(int o, uint32_t nonce, double, mi355x_datapath_attn_result* r) {
+  return needs_hsa_build("--datapath-attn", blank_result<mi355x_datapath_attn_result>(o, nonce), r);
 }
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
   auto blank = blank_result<mi355x_perf_result>(o, nonce);
@@ -420,7 +434,7 @@ bool run_on_each(const std::vector<int>& ords, const std::vector<uint32_t>& nonc
 }
 
 // --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16 /
-// --datapath-f64 / --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk and the server's requests
+// --datapath-f64 / --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk / --datapath-attn and the server's requests
 // of those kinds.
 // `iters`: the sweep's tile iterations or the throughput check's MFMA
 // iterations; `bytes`: the throughput check's HBM buffer.
@@ -470,12 +484,16 @@ bool run_check(const std::string& kind, const std::vector<int>& ords, const std:
     return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_splitk_result* r) {
       return datapath_splitk_check(o, nonce, t, r);
     }, datapath_splitk_json, json);
+  if (kind == "datapath_attn")
+    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_attn_result* r) {
+      return datapath_attn_check(o, nonce, t, r);
+    }, datapath_attn_json, json);
   return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_result* r) {
     return datapath_check(o, nonce, t, r);
   }, datapath_json, json);
 }
 
-// "S:W:B" or "S:W:B@O" of --corrupt-datapath and of its -i8, -bf16, -fp8, -f16, -f64, -f6f4, -sparse, -gemm and -splitk siblings
+// "S:W:B" or "S:W:B@O" of --corrupt-datapath and of its -i8, -bf16, -fp8, -f16, -f64, -f6f4, -sparse, -gemm, -splitk and -attn siblings
 bool parse_corrupt_datapath(const char* spec, int out[4]) {
   out[3] = -1;
   char tail = 0;
@@ -507,6 +525,7 @@ std::string devices_json(const std::vector<mi355x_probe_result>& results) {
 //     [@<id> ]datapath_sparse <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_gemm <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_splitk <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_attn <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // is answered with one JSON line {"id":..,"ok":..,"t_ready_ns":..,"devices":[..]}
 // ("id" only for a tagged request). A device's own deadline replaces the
 // request's timeout for that device: the plugin gives GPUs that run other
@@ -670,6 +689,7 @@ int main(int argc, char** argv) {
   bool datapath_sparse_mode = false;
   bool datapath_gemm_mode = false;
   bool datapath_splitk_mode = false;
+  bool datapath_attn_mode = false;
   uint64_t perf_mib = 4096;
   int perf_iters = 1 << 16;
   uint64_t peer_bytes = 64ull << 20;
@@ -801,6 +821,15 @@ int main(int argc, char** argv) {
         return 2;
       }
       datapath_splitk_corrupt(c[0], c[1], c[2], c[3]);
+    } else if (a == "--datapath-attn") {
+      datapath_attn_mode = true;
+    } else if (a == "--corrupt-datapath-attn") {
+      int c[4];
+      if (!parse_corrupt_datapath(next("--corrupt-datapath-attn"), c)) {
+        std::fprintf(stderr, "--corrupt-datapath-attn must be STAGE:WORD:BIT[@ORDINAL]\n");
+        return 2;
+      }
+      datapath_attn_corrupt(c[0], c[1], c[2], c[3]);
     } else if (a == "--perf-mib") {
       perf_mib = std::strtoull(next("--perf-mib"), nullptr, 0);
     } else if (a == "--perf-iters") {
@@ -833,6 +862,7 @@ int main(int argc, char** argv) {
                   "[--datapath-sparse [--corrupt-datapath-sparse S:W:B[@ORDINAL]]] "
                   "[--datapath-gemm [--corrupt-datapath-gemm S:W:B[@ORDINAL]]] "
                   "[--datapath-splitk [--corrupt-datapath-splitk S:W:B[@ORDINAL]]] "
+                  "[--datapath-attn [--corrupt-datapath-attn S:W:B[@ORDINAL]]] "
                   "[--corrupt-word K[@ORDINAL]] [--hip-stream own|null]\n",
                   argv[0]);
       return 0;
@@ -883,12 +913,13 @@ int main(int argc, char** argv) {
   const std::vector<double> timeouts(ords.size(), timeout_s);
   if (perf_mode || datapath_mode || datapath_i8_mode || datapath_bf16_mode || datapath_fp8_mode ||
       datapath_f16_mode || datapath_f64_mode || datapath_f6f4_mode || datapath_sparse_mode || datapath_gemm_mode ||
-      datapath_splitk_mode || sweep_mode) {
+      datapath_splitk_mode || datapath_attn_mode || sweep_mode) {
     const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : datapath_i8_mode ? "datapath_i8"
                        : datapath_bf16_mode ? "datapath_bf16" : datapath_fp8_mode ? "datapath_fp8"
                        : datapath_f16_mode ? "datapath_f16" : datapath_f64_mode ? "datapath_f64"
                        : datapath_f6f4_mode ? "datapath_f6f4" : datapath_sparse_mode ? "datapath_sparse"
-                       : datapath_gemm_mode ? "datapath_gemm" : datapath_splitk_mode ? "datapath_splitk" : "sweep";
+                       : datapath_gemm_mode ? "datapath_gemm" : datapath_splitk_mode ? "datapath_splitk"
+                       : datapath_attn_mode ? "datapath_attn" : "sweep";
     std::string body;
     const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
     std::printf("%s\n", mi355x::oneshot_check_json(kind, ok, n, t_start, t_runtime, mono_ns(), body).c_str());

@@ -14,6 +14,7 @@
 //     [@<id> ]datapath_sparse <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_gemm <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]datapath_splitk <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]datapath_attn <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 // A device's own deadline (> 0) replaces the request's timeout for that device.
 #pragma once
 
@@ -30,7 +31,8 @@ struct ServeRequest {
   bool tagged = false;
   unsigned long long id = 0;
   std::string kind;  // probe | sweep | perf | datapath | datapath_i8 | datapath_bf16 | datapath_fp8 | datapath_f16 |
-                     // datapath_f64 | datapath_f6f4 | datapath_sparse | datapath_gemm | datapath_splitk
+                     // datapath_f64 | datapath_f6f4 | datapath_sparse | datapath_gemm | datapath_splitk |
+                     // datapath_attn
   int iters = 0;
   double timeout_s = 0;
   unsigned long long perf_mib = 0;
@@ -91,6 +93,9 @@ inline bool parse_request(const std::string& line, ServeRequest* r) {
   } else if (std::strncmp(p, "datapath_splitk ", 16) == 0) {
     r->kind = "datapath_splitk";
     parsed = std::sscanf(p, "datapath_splitk %lf %n", &r->timeout_s, &consumed) >= 1;
+  } else if (std::strncmp(p, "datapath_attn ", 14) == 0) {
+    r->kind = "datapath_attn";
+    parsed = std::sscanf(p, "datapath_attn %lf %n", &r->timeout_s, &consumed) >= 1;
   } else if (std::strncmp(p, "datapath ", 9) == 0) {
     r->kind = "datapath";
     parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;

@@ -207,6 +207,32 @@ def datapath_splitk_verdict(cli, image: bytes, tiles: int, splits: int, ksteps: 
                           capture_output=True, text=True, timeout=120)
 
 
+def datapath_attn_cli(build_dir: Path) -> Path:
+    """native/tests/datapath_attn_contract_cli.cpp, found or compiled like contract_cli()."""
+    from .. import _build
+    exe = _build.DATAPATH_ATTN_CLI
+    if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
+        return exe
+    return compile_cli(Path(build_dir) / "datapath_attn_contract_cli",
+                       source=REPO / "native" / "tests" / "datapath_attn_contract_cli.cpp")
+
+
+def datapath_attn_image(cli, heads: int, qblocks: int, kblocks: int, nonce: int) -> bytes:
+    """`datapath_attn_contract_cli image`: the header's records, m / l words and O words, as bytes."""
+    return subprocess.run([str(cli), "image", str(heads), str(qblocks), str(kblocks), str(nonce)], capture_output=True,
+                          check=True, timeout=120).stdout
+
+
+def datapath_attn_verdict(cli, image: bytes, heads: int, qblocks: int, kblocks: int, nonce: int,
+                          work) -> subprocess.CompletedProcess:
+    """`datapath_attn_contract_cli verdict` on `image`, written into the directory `work`: stdout is one
+    datapath_attn_json line; exit 2 and no line for an image of another length."""
+    path = Path(work) / "datapath_attn_image.bin"
+    path.write_bytes(image)
+    return subprocess.run([str(cli), "verdict", str(heads), str(qblocks), str(kblocks), str(nonce), str(path)],
+                          capture_output=True, text=True, timeout=120)
+
+
 def _variants_blob(variants) -> bytes:
     out = []
     for patches in variants:

@@ -5,7 +5,8 @@ The stub answers a sweep, a throughput check or a datapath check with figures
 written into its source. They are true figures only if the real verdict
 (chip_verify.h, datapath_verify.h, datapath_i8_verify.h, datapath_bf16_verify.h,
 datapath_fp8_verify.h, datapath_f16_verify.h, datapath_f64_verify.h, datapath_f6f4_verify.h,
-datapath_sparse_verify.h, datapath_gemm_verify.h, datapath_splitk_verify.h) says the same of the
+datapath_sparse_verify.h, datapath_gemm_verify.h, datapath_splitk_verify.h,
+datapath_attn_verify.h) says the same of the
 fault the mode names, so every mode is defined here as a change to healthy
 records (testing/kernel_reference.py, datapath_reference.py and
 datapath_i8_reference.py build those), and `real_replies` runs the contract
@@ -30,6 +31,7 @@ from . import datapath_i8_reference as dpi8
 from . import datapath_sparse_reference as dpsp
 from . import datapath_gemm_reference as dpgm
 from . import datapath_splitk_reference as dpsk
+from . import datapath_attn_reference as dpat
 from . import datapath_reference as dp
 from . import kernel_reference as ref
 
@@ -57,11 +59,12 @@ DATAPATH_KEYS = ("ok", "grid", "records_ok", "mfma_bad", "stage_bad", "tile_bad"
 KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "datapath_i8": DATAPATH_KEYS,
         "datapath_bf16": DATAPATH_KEYS, "datapath_fp8": DATAPATH_KEYS, "datapath_f16": DATAPATH_KEYS,
         "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS, "datapath_sparse": DATAPATH_KEYS,
-        "datapath_gemm": DATAPATH_KEYS, "datapath_splitk": DATAPATH_KEYS + ("tiles", "splits", "ledger_bad")}
+        "datapath_gemm": DATAPATH_KEYS, "datapath_splitk": DATAPATH_KEYS + ("tiles", "splits", "ledger_bad"),
+        "datapath_attn": DATAPATH_KEYS + ("heads", "qblocks", "kblocks", "exp_inexact")}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
          "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES,
          "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES, "datapath_sparse": DATAPATH_MODES,
-         "datapath_gemm": DATAPATH_MODES, "datapath_splitk": DATAPATH_MODES}
+         "datapath_gemm": DATAPATH_MODES, "datapath_splitk": DATAPATH_MODES, "datapath_attn": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -289,6 +292,30 @@ def datapath_splitk_replies(build_dir) -> list:
     return out
 
 
+def datapath_attn_replies(build_dir) -> list:
+    """As datapath_gemm_replies for the attention check at the production sizes (GRID / 4 heads, 4 query blocks, 4 key
+    blocks). stuck_bit: bit 30 of the 64 O words of query 0 of workgroup WG; missing: workgroups WG and WG + 1 wrote no
+    record; device_bad: the first K fold sum of workgroup WG is off by 12."""
+    cli = contract_cli.datapath_attn_cli(build_dir)
+    sizes = (GRID // dpat.CUS_PER_HEAD, dpat.QBLOCKS, dpat.KBLOCKS, NONCE)
+    healthy = np.frombuffer(contract_cli.datapath_attn_image(cli, *sizes), dtype="<u4")
+    out = []
+    for mode in MODES["datapath_attn"]:
+        recs, ml, o = (x.copy() for x in np.split(healthy, [GRID * dpat.REC_WORDS, GRID * (dpat.REC_WORDS + dpat.ML_WORDS)]))
+        if mode == "stuck_bit":
+            o.reshape(GRID, dpat.O_WORDS)[WG, :dpat.D] &= np.uint32(~(1 << BIT) & 0xFFFFFFFF)
+        elif mode == "missing":
+            recs.reshape(GRID, dpat.REC_WORDS)[WG:WG + 2, :] = 0
+        elif mode == "device_bad":
+            recs.reshape(GRID, dpat.REC_WORDS)[WG, dpat.fold_slot(0, 1)] += 12
+        else:
+            assert mode == "ok", mode
+        r = contract_cli.datapath_attn_verdict(cli, dpat.image_bytes(recs, ml, o), *sizes, build_dir)
+        assert r.returncode == 0, r.stderr
+        out.append(json.loads(r.stdout))
+    return out
+
+
 def real_replies(kind: str, build_dir) -> dict:
     """mode -> the device object the shipped verdict and printer give for it."""
     modes = MODES[kind]
@@ -320,6 +347,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = datapath_gemm_replies(build_dir)
     elif kind == "datapath_splitk":
         out = datapath_splitk_replies(build_dir)
+    elif kind == "datapath_attn":
+        out = datapath_attn_replies(build_dir)
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:

@@ -30,6 +30,11 @@ REQUESTS.json is a list of requests, run in order:
         workgroups, t * s or launch_grid; with the inject build "inject" is {"kind": "atomic" or "drop", "wg": w,
         "wave": v, "lane": l, "index": accumulator word 0..63, "mask": m})
 
+    {"id": ..., "kernel": "datapath_attn", "nonce": n, "heads": h, "qblocks": q, "kblocks": k[, "launch_grid": ...]}
+        (mi355x_attn_fill, then mi355x_mfma_datapath_attn, on the same arguments and workgroups, h * q or launch_grid;
+        with the inject build "inject" is {"kind": "s" or "o", "wg": w, "wave": v, "lane": l, "index": accumulator word,
+        "mask": m})
+
 A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64, datapath_f6f4 or datapath_sparse request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
 the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h /
@@ -249,6 +254,21 @@ class DatapathSplitkInjectArgs(ctypes.Structure):
 DATAPATH_SPLITK_ARG_STRUCTS = {"mi355x_datapath_splitk_args": DatapathSplitkArgs}
 DATAPATH_SPLITK_INJECT_ARG_STRUCTS = {"mi355x_datapath_splitk_args": DatapathSplitkInjectArgs}
 DATAPATH_SPLITK_INJECT_KINDS = {"none": 0, "atomic": 1, "drop": 2}   # MI355X_DPSK_INJECT_*
+
+
+class DatapathAttnArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("ml", _ptr), ("o", _ptr), ("q", _ptr), ("k", _ptr), ("v", _ptr),
+                ("nonce", _u32), ("heads", _u32), ("qblocks", _u32), ("kblocks", _u32)]
+
+
+class DatapathAttnInjectArgs(ctypes.Structure):
+    _fields_ = DatapathAttnArgs._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_attn_kernel.h; both kernels of the check take the one struct
+DATAPATH_ATTN_ARG_STRUCTS = {"mi355x_datapath_attn_args": DatapathAttnArgs}
+DATAPATH_ATTN_INJECT_ARG_STRUCTS = {"mi355x_datapath_attn_args": DatapathAttnInjectArgs}
+DATAPATH_ATTN_INJECT_KINDS = {"none": 0, "s": 1, "o": 2}   # MI355X_DPAT_INJECT_*
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -264,6 +284,9 @@ def inject_words(req: dict) -> tuple:
     if req["kernel"] == "datapath_splitk":
         return (DATAPATH_SPLITK_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj["wave"]), int(inj["lane"]),
                 int(inj["index"]), int(inj.get("mask", 0)) & 0xFFFFFFFF)
+    if req["kernel"] == "datapath_attn":
+        return (DATAPATH_ATTN_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj["wave"]), int(inj["lane"]),
+                int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
     kind = INJECT_KINDS[inj["kind"]]
     if req["kernel"] in ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                          "datapath_f16", "datapath_f64", "datapath_f6f4", "datapath_sparse") and inj["kind"] == "lds":
@@ -278,7 +301,8 @@ def code_object_of(req: dict) -> str:
         raise ValueError(f"unknown code object {which!r}")
     if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                                                    "datapath_f16", "datapath_f64", "datapath_f6f4",
-                                                   "datapath_sparse", "datapath_gemm", "datapath_splitk"):
+                                                   "datapath_sparse", "datapath_gemm", "datapath_splitk",
+                                                   "datapath_attn"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -297,9 +321,11 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "datapath_f6f4": ("mi355x_mfma_datapath_f6f4", 256),
            "datapath_sparse": ("mi355x_mfma_datapath_sparse", 256),
            "datapath_gemm": ("mi355x_mfma_datapath_gemm", 256),
-           "datapath_splitk": ("mi355x_mfma_datapath_splitk", 256)}
+           "datapath_splitk": ("mi355x_mfma_datapath_splitk", 256),
+           "datapath_attn": ("mi355x_mfma_datapath_attn", 256)}
 # kernel -> (symbol, lanes) of a kernel launched before it (FIRST) or after it (LAST), on the same arguments and workgroups
-FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256), "datapath_splitk": ("mi355x_splitk_fill", 256)}
+FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256), "datapath_splitk": ("mi355x_splitk_fill", 256),
+         "datapath_attn": ("mi355x_attn_fill", 256)}
 LAST = {"datapath_splitk": ("mi355x_splitk_drain", 256)}
 
 _H2D, _D2H = 1, 2
@@ -530,6 +556,23 @@ def plan(req: dict, base_dir: Path):
         cls, tail = (DatapathSplitkInjectArgs, inject_words(req)) if inject else (DatapathSplitkArgs, ())
         return bufs, lambda p: cls(p["records"], p["tiles"], p["out_ledger"], p["a"], p["b"], p["d"], p["ledger"],
                                    req["nonce"], t, sp, ksteps, *tail), wgs
+    if k == "datapath_attn":
+        h, qb, kb = int(req["heads"]), int(req["qblocks"]), int(req["kblocks"])
+        if h < 1 or qb < 1 or h * qb > 65536 or not 1 <= kb <= 8:
+            raise ValueError("heads, qblocks, kblocks: outside what the kernels accept")   # the buffers are sized by them
+        bufs = [("records", np.uint32, _filled(h * qb * 32 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(h * qb * 128 * 64 * 4, OUT_PREFILL)),        # O
+                ("ml", np.uint32, _filled(h * qb * 128 * 2 * 4, OUT_PREFILL)),
+                ("q", np.uint16, _filled(h * qb * 128 * 64 * 2, OUT_PREFILL)),
+                ("k", np.uint16, _filled(h * kb * 64 * 64 * 2, OUT_PREFILL)),
+                ("v", np.uint16, _filled(h * kb * 64 * 64 * 2, OUT_PREFILL))]
+        inject = code_object_of(req) == "inject"
+        wgs = h * qb if inject else int(req.get("launch_grid", h * qb))
+        if wgs < h * qb:
+            raise ValueError("launch_grid below heads * qblocks")
+        cls, tail = (DatapathAttnInjectArgs, inject_words(req)) if inject else (DatapathAttnArgs, ())
+        return bufs, lambda p: cls(p["records"], p["ml"], p["tiles"], p["q"], p["k"], p["v"], req["nonce"], h, qb, kb,
+                                   *tail), wgs
     raise ValueError(f"unknown kernel {k!r}")
 
 

@@ -49,6 +49,8 @@ bf16 GEMM pipeline-check replies ("datapath_gemm" requests /
 --datapath-gemm) follow the "datapath_gemm" map and append "datapath_gemm:<host ordinal>".
 Split-K GEMM check replies ("datapath_splitk" requests /
 --datapath-splitk) follow the "datapath_splitk" map and append "datapath_splitk:<host ordinal>".
+Fused attention check replies ("datapath_attn" requests /
+--datapath-attn) follow the "datapath_attn" map and append "datapath_attn:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
 --iters) is appended to $MI355X_STUB_PROBE_ITERS_LOG if set, as "<kind> <iters>".
 Every line --serve reads and every line it writes back is appended to
@@ -104,7 +106,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
 
 
 DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16", "datapath_f64",
-                  "datapath_f6f4", "datapath_sparse", "datapath_gemm", "datapath_splitk")
+                  "datapath_f6f4", "datapath_sparse", "datapath_gemm", "datapath_splitk", "datapath_attn")
 
 
 def _log_check(kind, host_ordinal):
@@ -358,6 +360,37 @@ def _datapath_splitk_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return d
 
 
+# the shipped verdict's figures for the attn kind's faults at nonce 0x5EED142F (testing/probe_contract.py builds them):
+# stuck_bit = bit 30 of the 64 O words of query 0 of workgroup 17 (36 of them have it set; its first word's healthy
+# value), device_bad = fold word 1 of the K feed of workgroup 17 off by 12 (its healthy value)
+STUCK_ATTN = (36, 17 * 8192, 3382874112)
+FEED_ATTN = (17 * 8 + 1, 539155616)
+
+
+def _datapath_attn_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """Fused attention check reply (kind "datapath_attn"; stages: K feed, V feed, m / l words, O words); the modes of
+    _datapath_device, from the control file's "datapath_attn" map."""
+    stuck = dict(records_ok=255, tile_bad=STUCK_ATTN[0], stage_bad=[0, 0, 0, STUCK_ATTN[0]], first_bad_wg=17,
+                 first_bad_stage=3, first_bad_word=STUCK_ATTN[1], first_bad_got=STUCK_ATTN[2] ^ 0x40000000,
+                 first_bad_want=STUCK_ATTN[2], first_bad_xor=0x40000000,
+                 error=f"255/256 workgroups exact (feed_bad=0 stat_bad=0 o_bad={STUCK_ATTN[0]}); first bad: workgroup 17 "
+                       f"stage 3 word {STUCK_ATTN[1]} xor 0x40000000 (bit 30)")
+    d = _datapath_reply(ordinal_reported, "ok" if mode in ("device_bad", "missing") else mode, nonce, host_ordinal, 4, stuck,
+                        40.0, 60000.0, kind="datapath_attn")
+    d.update(heads=64, qblocks=4, kblocks=4, exp_inexact=0, fill_us=30.0, verify_us=50000.0)
+    if mode == "missing":
+        d.update(ok=False, records_ok=254, cus_covered=254, simds_covered=1016,
+                 error="254/256 workgroups exact (feed_bad=0 stat_bad=0 o_bad=0)")
+    elif mode == "device_bad":
+        got = FEED_ATTN[1] + 12
+        d.update(ok=False, records_ok=255, mfma_bad=1, stage_bad=[1, 0, 0, 0], first_bad_wg=17, first_bad_stage=0,
+                 first_bad_word=FEED_ATTN[0], first_bad_got=got, first_bad_want=FEED_ATTN[1],
+                 first_bad_xor=got ^ FEED_ATTN[1],
+                 error=f"255/256 workgroups exact (feed_bad=1 stat_bad=0 o_bad=0); first bad: workgroup 17 stage 0 word "
+                       f"{FEED_ATTN[0]} xor 0x{got ^ FEED_ATTN[1]:08x}")
+    return d
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
                 "datapath_fp8": _datapath_fp8_device,
@@ -366,7 +399,8 @@ CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datap
                 "datapath_f6f4": _datapath_f6f4_device,
                 "datapath_sparse": _datapath_sparse_device,
                 "datapath_gemm": _datapath_gemm_device,
-                "datapath_splitk": _datapath_splitk_device}
+                "datapath_splitk": _datapath_splitk_device,
+                "datapath_attn": _datapath_attn_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -444,6 +478,7 @@ _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapa
           ("datapath_sparse", (_FLOAT,)),
           ("datapath_gemm", (_FLOAT,)),
           ("datapath_splitk", (_FLOAT,)),
+          ("datapath_attn", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -740,6 +775,7 @@ def main(argv):
                        ("--datapath-sparse", "datapath_sparse"),
                        ("--datapath-gemm", "datapath_gemm"),
                        ("--datapath-splitk", "datapath_splitk"),
+                       ("--datapath-attn", "datapath_attn"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
