@@ -85,6 +85,50 @@ py::dict datapath_dict(const R& r) {
   return d;
 }
 
+// what the GEMM, split-K and attention results carry beyond datapath_dict
+template <typename R>
+void add_extras(py::dict&, const R&) {}
+void add_extras(py::dict& d, const mi355x_datapath_gemm_result& r) {
+  d["ksteps"] = r.ksteps;
+  d["fill_us"] = r.fill_us;
+}
+void add_extras(py::dict& d, const mi355x_datapath_splitk_result& r) {
+  d["tiles"] = r.tiles;
+  d["splits"] = r.splits;
+  d["ksteps"] = r.ksteps;
+  d["ledger_bad"] = r.ledger_bad;
+  d["xccs_per_tile_min"] = r.xccs_per_tile_min;
+  d["fill_us"] = r.fill_us;
+  d["drain_us"] = r.drain_us;
+  d["verify_us"] = r.verify_us;
+}
+void add_extras(py::dict& d, const mi355x_datapath_attn_result& r) {
+  d["heads"] = r.heads;
+  d["qblocks"] = r.qblocks;
+  d["kblocks"] = r.kblocks;
+  d["exp_inexact"] = r.exp_inexact;
+  d["fill_us"] = r.fill_us;
+  d["verify_us"] = r.verify_us;
+}
+
+// one datapath check's binding: the check with the GIL released, its result as a dict
+template <typename R>
+void def_datapath_check(py::module_& m, const char* name, int (*check)(int, uint32_t, double, R*)) {
+  m.def(
+      name,
+      [check](int ordinal, uint32_t nonce, double timeout_s) {
+        R r;
+        {
+          py::gil_scoped_release nogil;
+          check(ordinal, nonce, timeout_s, &r);
+        }
+        py::dict d = datapath_dict(r);
+        add_extras(d, r);
+        return d;
+      },
+      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+}
+
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "gfx950 MFMA liveness probe (in-process)";
   m.def("device_count", [] {
@@ -165,144 +209,15 @@ PYBIND11_MODULE(_hip, m) {
         return to_dict(r);
       },
       py::arg("ordinal") = 0);
-  m.def(
-      "hsa_datapath_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_i8_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_i8_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_i8_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_bf16_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_bf16_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_bf16_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_fp8_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_fp8_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_fp8_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_f16_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_f16_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_f16_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_f64_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_f64_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_f64_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_f6f4_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_f6f4_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_f6f4_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_sparse_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_sparse_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_sparse_check(ordinal, nonce, timeout_s, &r);
-        }
-        return datapath_dict(r);
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_gemm_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_gemm_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_gemm_check(ordinal, nonce, timeout_s, &r);
-        }
-        py::dict d = datapath_dict(r);
-        d["ksteps"] = r.ksteps;
-        d["fill_us"] = r.fill_us;
-        return d;
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_splitk_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_splitk_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_splitk_check(ordinal, nonce, timeout_s, &r);
-        }
-        py::dict d = datapath_dict(r);
-        d["tiles"] = r.tiles;
-        d["splits"] = r.splits;
-        d["ksteps"] = r.ksteps;
-        d["ledger_bad"] = r.ledger_bad;
-        d["xccs_per_tile_min"] = r.xccs_per_tile_min;
-        d["fill_us"] = r.fill_us;
-        d["drain_us"] = r.drain_us;
-        d["verify_us"] = r.verify_us;
-        return d;
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
-  m.def(
-      "hsa_datapath_attn_check",
-      [](int ordinal, uint32_t nonce, double timeout_s) {
-        mi355x_datapath_attn_result r;
-        {
-          py::gil_scoped_release nogil;
-          mi355x_hsa_datapath_attn_check(ordinal, nonce, timeout_s, &r);
-        }
-        py::dict d = datapath_dict(r);
-        d["heads"] = r.heads;
-        d["qblocks"] = r.qblocks;
-        d["kblocks"] = r.kblocks;
-        d["exp_inexact"] = r.exp_inexact;
-        d["fill_us"] = r.fill_us;
-        d["verify_us"] = r.verify_us;
-        return d;
-      },
-      py::arg("ordinal") = 0, py::arg("nonce") = 12345u, py::arg("timeout_s") = 5.0);
+  def_datapath_check(m, "hsa_datapath_check", mi355x_hsa_datapath_check);
+  def_datapath_check(m, "hsa_datapath_i8_check", mi355x_hsa_datapath_i8_check);
+  def_datapath_check(m, "hsa_datapath_bf16_check", mi355x_hsa_datapath_bf16_check);
+  def_datapath_check(m, "hsa_datapath_fp8_check", mi355x_hsa_datapath_fp8_check);
+  def_datapath_check(m, "hsa_datapath_f16_check", mi355x_hsa_datapath_f16_check);
+  def_datapath_check(m, "hsa_datapath_f64_check", mi355x_hsa_datapath_f64_check);
+  def_datapath_check(m, "hsa_datapath_f6f4_check", mi355x_hsa_datapath_f6f4_check);
+  def_datapath_check(m, "hsa_datapath_sparse_check", mi355x_hsa_datapath_sparse_check);
+  def_datapath_check(m, "hsa_datapath_gemm_check", mi355x_hsa_datapath_gemm_check);
+  def_datapath_check(m, "hsa_datapath_splitk_check", mi355x_hsa_datapath_splitk_check);
+  def_datapath_check(m, "hsa_datapath_attn_check", mi355x_hsa_datapath_attn_check);
 }

@@ -4,6 +4,7 @@
 #include <map>
 #include <set>
 
+#include "../health/probe_kinds.h"
 #include "mi355x/goflag.h"
 
 namespace mi355x::daemon {
@@ -158,28 +159,12 @@ bool parse_flags(int argc, char** argv, Flags* f, std::string* err, bool* help, 
            false;
   if (f->perf_check_every > 0 && !f->liveness)
     return *err = "perf_check_every needs -liveness (the throughput check runs in the probe server)", false;
-  if (f->datapath_check_every > 0 && !f->liveness)
-    return *err = "datapath_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_i8_check_every > 0 && !f->liveness)
-    return *err = "datapath_i8_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_bf16_check_every > 0 && !f->liveness)
-    return *err = "datapath_bf16_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_fp8_check_every > 0 && !f->liveness)
-    return *err = "datapath_fp8_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_f16_check_every > 0 && !f->liveness)
-    return *err = "datapath_f16_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_f64_check_every > 0 && !f->liveness)
-    return *err = "datapath_f64_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_f6f4_check_every > 0 && !f->liveness)
-    return *err = "datapath_f6f4_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_sparse_check_every > 0 && !f->liveness)
-    return *err = "datapath_sparse_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_gemm_check_every > 0 && !f->liveness)
-    return *err = "datapath_gemm_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_splitk_check_every > 0 && !f->liveness)
-    return *err = "datapath_splitk_check_every needs -liveness (the datapath check runs in the probe server)", false;
-  if (f->datapath_attn_check_every > 0 && !f->liveness)
-    return *err = "datapath_attn_check_every needs -liveness (the datapath check runs in the probe server)", false;
+  // every datapath kind's -<kind>_check_every, in the order of probe_kinds.h (the first one set is named)
+  for (const ProbeKind& k : kProbeKinds) {
+    const std::string name = std::string(k.wire) + "_check_every";
+    if (*ints.at(name) > 0 && !f->liveness)
+      return *err = name + " needs -liveness (the datapath check runs in the probe server)", false;
+  }
   return true;
 }
 

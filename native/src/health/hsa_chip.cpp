@@ -45,6 +45,7 @@
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_json.h"
+#include "probe_kinds.h"
 #include "probe_verify.h"
 
 using namespace mi355x::hsa_rt;  // NOLINT(build/namespaces)
@@ -425,19 +426,64 @@ struct Check {
 };
 
 std::atomic<uint64_t> g_perf_poison{~0ull};
-// --corrupt-datapath: stage < 0 = off
+// --corrupt-datapath*: per kind (a row of probe_kinds.h) stage, word, bit, ordinal; stage < 0 = off
 std::mutex g_dp_corrupt_mu;
-int g_dp_corrupt[4] = {-1, 0, 0, -1};  // stage, word, bit, ordinal
-int g_dpi8_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-i8, likewise
-int g_dpbf_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-bf16, likewise
-int g_dpf8_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-fp8, likewise
-int g_dphf_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f16, likewise
-int g_dpd_corrupt[4] = {-1, 0, 0, -1};   // --corrupt-datapath-f64, likewise
-int g_dpf6_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-f6f4, likewise
-int g_dpsp_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-sparse, likewise
-int g_dpgm_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-gemm, likewise
-int g_dpsk_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-splitk, likewise
-int g_dpat_corrupt[4] = {-1, 0, 0, -1};  // --corrupt-datapath-attn, likewise
+struct DpCorrupt {
+  int v[4] = {-1, 0, 0, -1};
+};
+DpCorrupt g_dp_corrupt[mi355x::kProbeKindCount];
+
+// the kind's injection; g_dp_corrupt_mu held
+int* dp_corrupt(const char* kind) { return g_dp_corrupt[mi355x::probe_kind_index(kind)].v; }
+
+void set_dp_corrupt(const char* kind, int stage, int word, int bit, int ordinal) {
+  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+  int* c = dp_corrupt(kind);
+  c[0] = stage;
+  c[1] = word;
+  c[2] = bit;
+  c[3] = ordinal;
+}
+
+// A register-only datapath check, described by its traits
+// (datapath_verdict_common.h): one kernel, one workgroup per CU, each writing a
+// record and wave 0's tiles into host memory, then the shared verdict.
+template <typename T>
+int register_datapath_check(int ordinal, uint32_t nonce, double timeout_s, typename T::Result* out) {
+  using R = typename T::Result;
+  using Args = typename T::Args;
+  *out = mi355x::blank_result<R>(ordinal, nonce);
+  Check<R> c(ordinal, timeout_s, out);
+  KernelInfo k;
+  // no device memory: records, tiles and kernargs all live in host pools
+  if (!c.begin(false, &R::grid, 1, T::kKind, {{T::kSymbol, sizeof(Args)}}, &k)) return 1;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
+  const size_t rec_bytes = static_cast<size_t>(grid) * T::kRecWords * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * T::kWgWords * sizeof(uint32_t);
+  auto* records = c.bufs.template alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.template alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  auto* kargs = c.bufs.template alloc<Args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  if (!c.run(k, kargs, grid, T::kThreads, T::kDispatch, &out->kernel_us)) return 1;
+  {
+    // workgroup 0's tiles: the word is numbered within its stage
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = dp_corrupt(T::kKind);
+    if (cr[0] >= 0 && cr[0] < static_cast<int>(T::kStages) && cr[1] >= 0 &&
+        cr[1] < static_cast<int>(T::tiles(cr[0]) * T::tile_words(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
+        (cr[3] < 0 || cr[3] == ordinal))
+      tiles[T::tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
+  }
+  mi355x::datapath_register_verdict<T>(records, tiles, grid, out);
+  return c.finish();
+}
 
 }  // namespace
 }  // namespace mi355x::hsa_rt
@@ -542,368 +588,70 @@ extern "C" int mi355x_hsa_perf_check(int ordinal, uint32_t nonce, uint64_t bytes
   return c.finish();
 }
 
-extern "C" void mi355x_hsa_datapath_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dp_corrupt[0] = stage;
-  g_dp_corrupt[1] = word;
-  g_dp_corrupt[2] = bit;
-  g_dp_corrupt[3] = ordinal;
-}
-
+// the eight register-only datapath checks and the eleven kinds' fault injection (liveness_probe.h)
 extern "C" int mi355x_hsa_datapath_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_result>(ordinal, nonce);
-  Check<mi355x_datapath_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_result::grid, 1, "datapath",
-               {{"mi355x_mfma_datapath.kd", sizeof(mi355x_datapath_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DP_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DP_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs = c.bufs.alloc<mi355x_datapath_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DP_THREADS, "datapath check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dp_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DP_STAGES && cr[1] >= 0 && cr[1] < MI355X_DP_TILE && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[cr[0] * MI355X_DP_TILE + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_verdict(records, tiles, grid, out);
-  return c.finish();
+  return register_datapath_check<mi355x::DatapathF32Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_i8_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpi8_corrupt[0] = stage;
-  g_dpi8_corrupt[1] = word;
-  g_dpi8_corrupt[2] = bit;
-  g_dpi8_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_i8_check(int ordinal, uint32_t nonce, double timeout_s,
                                             mi355x_datapath_i8_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_i8_result>(ordinal, nonce);
-  Check<mi355x_datapath_i8_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_i8_result::grid, 1, "datapath_i8",
-               {{"mi355x_mfma_datapath_i8.kd", sizeof(mi355x_datapath_i8_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPI8_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPI8_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_i8_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPI8_THREADS, "datapath i8 check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpi8_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPI8_STAGES && cr[1] >= 0 &&
-        cr[1] < static_cast<int>(dpi8_dim(cr[0]) * dpi8_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dpi8_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_i8_verdict(records, tiles, grid, out);
-  return c.finish();
+  return register_datapath_check<mi355x::DatapathI8Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_bf16_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpbf_corrupt[0] = stage;
-  g_dpbf_corrupt[1] = word;
-  g_dpbf_corrupt[2] = bit;
-  g_dpbf_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_bf16_check(int ordinal, uint32_t nonce, double timeout_s,
-                                            mi355x_datapath_bf16_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_bf16_result>(ordinal, nonce);
-  Check<mi355x_datapath_bf16_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_bf16_result::grid, 1, "datapath_bf16",
-               {{"mi355x_mfma_datapath_bf16.kd", sizeof(mi355x_datapath_bf16_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPBF_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPBF_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_bf16_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPBF_THREADS, "datapath bf16 check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpbf_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPBF_STAGES && cr[1] >= 0 &&
-        cr[1] < static_cast<int>(dpbf_dim(cr[0]) * dpbf_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dpbf_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_bf16_verdict(records, tiles, grid, out);
-  return c.finish();
+                                              mi355x_datapath_bf16_result* out) {
+  return register_datapath_check<mi355x::DatapathBf16Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_fp8_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpf8_corrupt[0] = stage;
-  g_dpf8_corrupt[1] = word;
-  g_dpf8_corrupt[2] = bit;
-  g_dpf8_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_fp8_check(int ordinal, uint32_t nonce, double timeout_s,
-                                           mi355x_datapath_fp8_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_fp8_result>(ordinal, nonce);
-  Check<mi355x_datapath_fp8_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_fp8_result::grid, 1, "datapath_fp8",
-               {{"mi355x_mfma_datapath_fp8.kd", sizeof(mi355x_datapath_fp8_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPF8_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPF8_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_fp8_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPF8_THREADS, "datapath fp8 check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpf8_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPF8_STAGES && cr[1] >= 0 &&
-        cr[1] < static_cast<int>(dpf8_dim(cr[0]) * dpf8_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dpf8_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_fp8_verdict(records, tiles, grid, out);
-  return c.finish();
+                                             mi355x_datapath_fp8_result* out) {
+  return register_datapath_check<mi355x::DatapathFp8Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_f16_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dphf_corrupt[0] = stage;
-  g_dphf_corrupt[1] = word;
-  g_dphf_corrupt[2] = bit;
-  g_dphf_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_f16_check(int ordinal, uint32_t nonce, double timeout_s,
-                                           mi355x_datapath_f16_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_f16_result>(ordinal, nonce);
-  Check<mi355x_datapath_f16_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_f16_result::grid, 1, "datapath_f16",
-               {{"mi355x_mfma_datapath_f16.kd", sizeof(mi355x_datapath_f16_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPHF_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPHF_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_f16_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPHF_THREADS, "datapath f16 check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dphf_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPHF_STAGES && cr[1] >= 0 &&
-        cr[1] < static_cast<int>(dphf_dim(cr[0]) * dphf_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dphf_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_f16_verdict(records, tiles, grid, out);
-  return c.finish();
+                                             mi355x_datapath_f16_result* out) {
+  return register_datapath_check<mi355x::DatapathF16Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_f64_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpd_corrupt[0] = stage;
-  g_dpd_corrupt[1] = word;
-  g_dpd_corrupt[2] = bit;
-  g_dpd_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_f64_check(int ordinal, uint32_t nonce, double timeout_s,
-                                           mi355x_datapath_f64_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_f64_result>(ordinal, nonce);
-  Check<mi355x_datapath_f64_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_f64_result::grid, 1, "datapath_f64",
-               {{"mi355x_mfma_datapath_f64.kd", sizeof(mi355x_datapath_f64_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPD_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPD_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_f64_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPD_THREADS, "datapath f64 check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpd_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPD_STAGES && cr[1] >= 0 && cr[1] < static_cast<int>(dpd_stage_words(cr[0])) &&
-        cr[2] >= 0 && cr[2] < 32 && (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dpd_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_f64_verdict(records, tiles, grid, out);
-  return c.finish();
+                                             mi355x_datapath_f64_result* out) {
+  return register_datapath_check<mi355x::DatapathF64Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_f6f4_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpf6_corrupt[0] = stage;
-  g_dpf6_corrupt[1] = word;
-  g_dpf6_corrupt[2] = bit;
-  g_dpf6_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_f6f4_check(int ordinal, uint32_t nonce, double timeout_s,
-                                            mi355x_datapath_f6f4_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_f6f4_result>(ordinal, nonce);
-  Check<mi355x_datapath_f6f4_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_f6f4_result::grid, 1, "datapath_f6f4",
-               {{"mi355x_mfma_datapath_f6f4.kd", sizeof(mi355x_datapath_f6f4_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPF6_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPF6_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_f6f4_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPF6_THREADS, "datapath f6f4 check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpf6_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPF6_STAGES && cr[1] >= 0 &&
-        cr[1] < static_cast<int>(dpf6_dim(cr[0]) * dpf6_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dpf6_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_f6f4_verdict(records, tiles, grid, out);
-  return c.finish();
+                                              mi355x_datapath_f6f4_result* out) {
+  return register_datapath_check<mi355x::DatapathF6f4Traits>(ordinal, nonce, timeout_s, out);
 }
-
-extern "C" void mi355x_hsa_datapath_sparse_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpsp_corrupt[0] = stage;
-  g_dpsp_corrupt[1] = word;
-  g_dpsp_corrupt[2] = bit;
-  g_dpsp_corrupt[3] = ordinal;
-}
-
 extern "C" int mi355x_hsa_datapath_sparse_check(int ordinal, uint32_t nonce, double timeout_s,
-                                            mi355x_datapath_sparse_result* out) {
-  *out = mi355x::blank_result<mi355x_datapath_sparse_result>(ordinal, nonce);
-  Check<mi355x_datapath_sparse_result> c(ordinal, timeout_s, out);
-  KernelInfo k;
-  // no device memory: records, tiles and kernargs all live in host pools
-  if (!c.begin(false, &mi355x_datapath_sparse_result::grid, 1, "datapath_sparse",
-               {{"mi355x_mfma_datapath_sparse.kd", sizeof(mi355x_datapath_sparse_args)}}, &k))
-    return 1;
-  const uint32_t grid = static_cast<uint32_t>(out->grid);
-  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPSP_REC_WORDS * sizeof(uint32_t);
-  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPSP_WG_WORDS * sizeof(uint32_t);
-  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
-  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
-  auto* kargs =
-      c.bufs.alloc<mi355x_datapath_sparse_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
-  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
-  std::memset(records, 0, rec_bytes);
-  std::memset(tiles, 0xFF, tile_bytes);
-  std::memset(kargs, 0, kKernargBytes);
-  kargs->records = records;
-  kargs->tiles = tiles;
-  kargs->nonce = nonce;
-  kargs->grid = grid;
-  if (!c.run(k, kargs, grid, MI355X_DPSP_THREADS, "datapath sparse check", &out->kernel_us)) return 1;
-  {
-    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpsp_corrupt;
-    if (cr[0] >= 0 && cr[0] < MI355X_DPSP_STAGES && cr[1] >= 0 &&
-        cr[1] < static_cast<int>(dpsp_dim(cr[0]) * dpsp_dim(cr[0])) && cr[2] >= 0 && cr[2] < 32 &&
-        (cr[3] < 0 || cr[3] == ordinal))
-      tiles[dpsp_tile_offset(cr[0]) + cr[1]] ^= 1u << cr[2];
-  }
-  mi355x::datapath_sparse_verdict(records, tiles, grid, out);
-  return c.finish();
+                                                mi355x_datapath_sparse_result* out) {
+  return register_datapath_check<mi355x::DatapathSparseTraits>(ordinal, nonce, timeout_s, out);
 }
-
+extern "C" void mi355x_hsa_datapath_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_i8_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_i8", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_bf16_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_bf16", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_fp8_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_fp8", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_f16_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_f16", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_f64_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_f64", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_f6f4_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_f6f4", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_sparse_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_sparse", stage, word, bit, ordinal);
+}
 extern "C" void mi355x_hsa_datapath_gemm_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpgm_corrupt[0] = stage;
-  g_dpgm_corrupt[1] = word;
-  g_dpgm_corrupt[2] = bit;
-  g_dpgm_corrupt[3] = ordinal;
+  set_dp_corrupt("datapath_gemm", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_splitk_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_splitk", stage, word, bit, ordinal);
+}
+extern "C" void mi355x_hsa_datapath_attn_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_attn", stage, word, bit, ordinal);
 }
 
 extern "C" int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, double timeout_s,
@@ -945,7 +693,7 @@ extern "C" int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, doubl
     return 1;
   {
     std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpgm_corrupt;
+    const int* cr = dp_corrupt("datapath_gemm");
     const int words = cr[0] == 2 ? MI355X_DPGM_WG_WORDS : 8;
     if (cr[0] >= 0 && cr[0] < MI355X_DPGM_STAGES && cr[1] >= 0 && cr[1] < words && cr[2] >= 0 && cr[2] < 32 &&
         (cr[3] < 0 || cr[3] == ordinal))
@@ -955,14 +703,6 @@ extern "C" int mi355x_hsa_datapath_gemm_check(int ordinal, uint32_t nonce, doubl
   mi355x::datapath_gemm_verdict(records, tiles, grid, MI355X_DPGM_KSTEPS, out);
   out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
-}
-
-extern "C" void mi355x_hsa_datapath_splitk_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpsk_corrupt[0] = stage;
-  g_dpsk_corrupt[1] = word;
-  g_dpsk_corrupt[2] = bit;
-  g_dpsk_corrupt[3] = ordinal;
 }
 
 extern "C" int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, double timeout_s,
@@ -1021,7 +761,7 @@ extern "C" int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, dou
     return 1;
   {
     std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpsk_corrupt;
+    const int* cr = dp_corrupt("datapath_splitk");
     const int words = static_cast<int>(cr[0] == 2 ? tiles * MI355X_DPSK_TILE_WORDS
                                        : cr[0] == 3 ? tiles * MI355X_DPSK_LEDGER_WORDS : grid * 8);
     if (cr[0] >= 0 && cr[0] < MI355X_DPSK_STAGES && cr[1] >= 0 && cr[1] < words && cr[2] >= 0 && cr[2] < 32 &&
@@ -1034,14 +774,6 @@ extern "C" int mi355x_hsa_datapath_splitk_check(int ordinal, uint32_t nonce, dou
   mi355x::datapath_splitk_verdict(records, out_d, out_led, tiles, MI355X_DPSK_SPLITS, MI355X_DPSK_KSTEPS, out);
   out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
-}
-
-extern "C" void mi355x_hsa_datapath_attn_corrupt(int stage, int word, int bit, int ordinal) {
-  std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-  g_dpat_corrupt[0] = stage;
-  g_dpat_corrupt[1] = word;
-  g_dpat_corrupt[2] = bit;
-  g_dpat_corrupt[3] = ordinal;
 }
 
 extern "C" int mi355x_hsa_datapath_attn_check(int ordinal, uint32_t nonce, double timeout_s,
@@ -1097,7 +829,7 @@ extern "C" int mi355x_hsa_datapath_attn_check(int ordinal, uint32_t nonce, doubl
     return 1;
   {
     std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
-    const int* cr = g_dpat_corrupt;
+    const int* cr = dp_corrupt("datapath_attn");
     const int words = static_cast<int>(cr[0] == 2 ? grid * MI355X_DPAT_ML_WORDS
                                        : cr[0] == 3 ? grid * MI355X_DPAT_O_WORDS : grid * 8);
     if (cr[0] >= 0 && cr[0] < MI355X_DPAT_STAGES && cr[1] >= 0 && cr[1] < words && cr[2] >= 0 && cr[2] < 32 &&

@@ -32,6 +32,7 @@
 #include "mi355x/grpc_server.h"
 #include "mi355x/smi_query.h"
 #include "mi355x/sysfs.h"
+#include "probe_kinds.h"
 
 extern char** environ;
 
@@ -443,17 +444,7 @@ std::map<int, ProbeOutcome> LivenessProber::spawn_all(const std::vector<int>& or
                                    std::string("--timeout"), std::string(tmo)})
         argv.push_back(a);
       if (kind == "sweep") argv.push_back("--sweep");
-      if (kind == "datapath") argv.push_back("--datapath");
-      if (kind == "datapath_i8") argv.push_back("--datapath-i8");
-      if (kind == "datapath_bf16") argv.push_back("--datapath-bf16");
-      if (kind == "datapath_fp8") argv.push_back("--datapath-fp8");
-      if (kind == "datapath_f16") argv.push_back("--datapath-f16");
-      if (kind == "datapath_f64") argv.push_back("--datapath-f64");
-      if (kind == "datapath_f6f4") argv.push_back("--datapath-f6f4");
-      if (kind == "datapath_sparse") argv.push_back("--datapath-sparse");
-      if (kind == "datapath_gemm") argv.push_back("--datapath-gemm");
-      if (kind == "datapath_splitk") argv.push_back("--datapath-splitk");
-      if (kind == "datapath_attn") argv.push_back("--datapath-attn");
+      if (const int dp = probe_kind_index(kind); dp >= 0) argv.push_back(probe_kind_flag(kProbeKinds[dp]));
       if (kind == "perf")
         for (const std::string& a : {std::string("--perf"), std::string("--perf-mib"), std::to_string(cfg_.perf_mib),
                                      std::string("--perf-iters"), std::to_string(cfg_.perf_iters)})
@@ -682,10 +673,7 @@ std::map<int, ProbeOutcome> LivenessProber::request(const std::shared_ptr<Server
   char head[96];
   if (kind == "perf")
     std::snprintf(head, sizeof(head), "perf %d %.3f %d", cfg_.perf_iters, top, cfg_.perf_mib);
-  else if (kind == "datapath" || kind == "datapath_i8" || kind == "datapath_bf16" ||
-           kind == "datapath_fp8" || kind == "datapath_f16" || kind == "datapath_f64" ||
-           kind == "datapath_f6f4" || kind == "datapath_sparse" || kind == "datapath_gemm" ||
-           kind == "datapath_splitk" || kind == "datapath_attn")
+  else if (probe_kind_index(kind) >= 0)
     std::snprintf(head, sizeof(head), "%s %.3f", kind.c_str(), top);
   else
     std::snprintf(head, sizeof(head), "%s %d %.3f", kind.c_str(), cfg_.iters, top);

@@ -1,5 +1,5 @@
 // The JSON the probe prints: a device's object for the liveness probe, a chip
-// sweep, a throughput check and the four datapath checks, the server's hello,
+// sweep, a throughput check and the datapath checks (probe_kinds.h), the server's hello,
 // and the lines around the devices, --serve and one-shot (shared by
 // probe_main.cpp and the contract CLIs under native/tests, so a test sees
 // exactly the line the prober parses), and the blank result each check starts
@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "mi355x/liveness_probe.h"
+#include "probe_kinds.h"
 
 namespace mi355x {
 
@@ -48,9 +49,15 @@ __attribute__((format(printf, 1, 2))) inline std::string json_format(const char*
   return o;
 }
 
+// the datapath results, and only they, have first_bad_wg / _stage / _word
+template <typename R, typename = void>
+struct has_first_bad : std::false_type {};
+template <typename R>
+struct has_first_bad<R, std::void_t<decltype(R::first_bad_wg)>> : std::true_type {};
+
 // The result of a check on `ordinal` before anything is known: all zero but
 // what the type defines otherwise -- the datapath results' first_bad_* = -1
-// ("none"), the four checks' kfd_node_id = -1 (with pci_bus_id "": the reply
+// ("none"), the checks' kfd_node_id = -1 (with pci_bus_id "": the reply
 // never reached a device). hbm_first_bad of the throughput result stays 0 here: a reply that
 // never reached the runtime carries 0, mi355x_hsa_perf_check sets its own -1.
 template <typename R>
@@ -58,15 +65,7 @@ R blank_result(int ordinal, uint32_t nonce) {
   R r{};
   r.ordinal = ordinal;
   r.nonce = nonce;
-  if constexpr (std::is_same_v<R, mi355x_datapath_result> || std::is_same_v<R, mi355x_datapath_i8_result> ||
-                std::is_same_v<R, mi355x_datapath_fp8_result> || std::is_same_v<R, mi355x_datapath_f16_result> ||
-                std::is_same_v<R, mi355x_datapath_f64_result> ||
-                std::is_same_v<R, mi355x_datapath_f6f4_result> ||
-                std::is_same_v<R, mi355x_datapath_sparse_result> ||
-                std::is_same_v<R, mi355x_datapath_gemm_result> ||
-                std::is_same_v<R, mi355x_datapath_splitk_result> ||
-                std::is_same_v<R, mi355x_datapath_attn_result>)
-    r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
+  if constexpr (has_first_bad<R>::value) r.first_bad_wg = r.first_bad_stage = r.first_bad_word = -1;
   if constexpr (!std::is_same_v<R, mi355x_probe_result>) r.kfd_node_id = -1;  // a check that names no agent
   return r;
 }
@@ -113,176 +112,70 @@ inline std::string perf_json(const mi355x_perf_result& r) {
       json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
 }
 
-inline std::string datapath_json(const mi355x_datapath_result& r) {
+// What a datapath kind's device object has beyond the common fields, as JSON
+// members with their trailing commas, at the four places such fields stand:
+// after "grid", after "tile_bad", after "xccs_covered" and after "kernel_us".
+// The register-only kinds have none.
+struct DatapathExtras {
+  std::string after_grid, after_tile_bad, after_coverage, after_kernel_us;
+};
+template <typename R>
+DatapathExtras datapath_extras(const R&) {
+  return {};
+}
+// ksteps, and the fill's GPU time and the verdict's host time beside the GEMM's
+inline DatapathExtras datapath_extras(const mi355x_datapath_gemm_result& r) {
+  return {json_format("\"ksteps\":%d,", r.ksteps), "", json_format("\"fill_us\":%.2f,", r.fill_us),
+          json_format("\"verify_us\":%.1f,", r.verify_us)};
+}
+// the tile and split counts, the ledger's bad words, the fewest XCDs that served one tile, the drain's GPU time
+inline DatapathExtras datapath_extras(const mi355x_datapath_splitk_result& r) {
+  return {json_format("\"tiles\":%d,\"splits\":%d,\"ksteps\":%d,", r.tiles, r.splits, r.ksteps),
+          json_format("\"ledger_bad\":%u,", r.ledger_bad),
+          json_format("\"xccs_per_tile_min\":%d,\"fill_us\":%.2f,", r.xccs_per_tile_min, r.fill_us),
+          json_format("\"drain_us\":%.2f,\"verify_us\":%.1f,", r.drain_us, r.verify_us)};
+}
+// the head and block counts and the count of inexact v_exp_f32 results
+inline DatapathExtras datapath_extras(const mi355x_datapath_attn_result& r) {
+  return {json_format("\"heads\":%d,\"qblocks\":%d,\"kblocks\":%d,", r.heads, r.qblocks, r.kblocks),
+          json_format("\"exp_inexact\":%u,", r.exp_inexact), json_format("\"fill_us\":%.2f,", r.fill_us),
+          json_format("\"verify_us\":%.1f,", r.verify_us)};
+}
+
+// The device object of every datapath kind: the common fields, the kind's
+// extras where they stand, and as many stage counts as the result holds.
+template <typename R>
+std::string datapath_device_json(const R& r) {
+  const DatapathExtras x = datapath_extras(r);
+  std::string stages;
+  for (const uint32_t s : r.stage_bad) stages += (stages.empty() ? "" : ",") + std::to_string(s);
   return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u],\"tile_bad\":%u,"
+      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,%s\"cu_count\":%d,\"num_xcc\":%d,"
+      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%s],\"tile_bad\":%u,%s"
       "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
+      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,%s"
+      "\"kernel_us\":%.2f,%s\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
       "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.tile_bad, r.first_bad_wg,
+      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, x.after_grid.c_str(), r.cu_count, r.num_xcc,
+      r.records_ok, r.mfma_bad, stages.c_str(), r.tile_bad, x.after_tile_bad.c_str(), r.first_bad_wg,
       r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered,
-      r.simds_covered, r.xccs_covered, r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-inline std::string datapath_i8_json(const mi355x_datapath_i8_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
-      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.tile_bad,
-      r.first_bad_wg, r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor,
-      r.cus_covered, r.simds_covered, r.xccs_covered, r.kernel_us, r.total_us, r.in_flight_s,
-      r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the bf16 check's result is the int8 check's (liveness_probe.h): the same line
-inline std::string datapath_bf16_json(const mi355x_datapath_bf16_result& r) { return datapath_i8_json(r); }
-
-// the fp8 check's line: the int8 check's with eight stage counts
-inline std::string datapath_fp8_json(const mi355x_datapath_fp8_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
-      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.stage_bad[5],
-      r.stage_bad[6], r.stage_bad[7], r.tile_bad, r.first_bad_wg, r.first_bad_stage, r.first_bad_word,
-      r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered, r.xccs_covered,
-      r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the f16 check's line: the int8 check's with seven stage counts
-inline std::string datapath_f16_json(const mi355x_datapath_f16_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
-      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.stage_bad[5],
-      r.stage_bad[6], r.tile_bad, r.first_bad_wg, r.first_bad_stage, r.first_bad_word,
-      r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered, r.xccs_covered,
-      r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the f64 check's line: the f16 check's, field for field
-inline std::string datapath_f64_json(const mi355x_datapath_f64_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
-      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.stage_bad[5],
-      r.stage_bad[6], r.tile_bad, r.first_bad_wg, r.first_bad_stage, r.first_bad_word,
-      r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered, r.xccs_covered,
-      r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the f64 check's line: the f16 check's, field for field
-inline std::string datapath_f6f4_json(const mi355x_datapath_f6f4_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
-      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.stage_bad[5],
-      r.stage_bad[6], r.stage_bad[7], r.tile_bad, r.first_bad_wg, r.first_bad_stage, r.first_bad_word,
-      r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered, r.xccs_covered,
-      r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the sparse check's line: the f16 check's, field for field, with ten stages
-inline std::string datapath_sparse_json(const mi355x_datapath_sparse_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u,%u,%u,%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"kernel_us\":%.2f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,"
-      "\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.stage_bad[4], r.stage_bad[5],
-      r.stage_bad[6], r.stage_bad[7], r.stage_bad[8], r.stage_bad[9], r.tile_bad, r.first_bad_wg, r.first_bad_stage,
-      r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered,
-      r.xccs_covered, r.kernel_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id,
-      json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the GEMM pipeline check's line: the siblings' fields with three stages (A feed, B feed, D words), and ksteps and
-// the fill's GPU time beside the GEMM's
-inline std::string datapath_gemm_json(const mi355x_datapath_gemm_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"ksteps\":%d,\"cu_count\":%d,\"num_xcc\":%d,"
-      "\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u],\"tile_bad\":%u,"
-      "\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"fill_us\":%.2f,\"kernel_us\":%.2f,\"verify_us\":%.1f,\"total_us\":%.1f,\"in_flight_s\":%.2f,\"kept_queue\":%s,"
-      "\"kfd_node_id\":%d,\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.ksteps, r.cu_count, r.num_xcc, r.records_ok,
-      r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.tile_bad, r.first_bad_wg, r.first_bad_stage,
-      r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor, r.cus_covered, r.simds_covered,
-      r.xccs_covered, r.fill_us, r.kernel_us, r.verify_us, r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false",
-      r.kfd_node_id, json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
-
-// the split-K GEMM check's line: the GEMM check's fields with four stages (A feed, B feed, D words, ledger), the tile
-// and split counts, the drain's GPU time and the fewest XCDs that served one tile
-inline std::string datapath_splitk_json(const mi355x_datapath_splitk_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"tiles\":%d,\"splits\":%d,\"ksteps\":%d,"
-      "\"cu_count\":%d,\"num_xcc\":%d,\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"ledger_bad\":%u,\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"xccs_per_tile_min\":%d,\"fill_us\":%.2f,\"kernel_us\":%.2f,\"drain_us\":%.2f,\"verify_us\":%.1f,\"total_us\":%.1f,"
-      "\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.tiles, r.splits, r.ksteps, r.cu_count, r.num_xcc,
-      r.records_ok, r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.tile_bad, r.ledger_bad,
-      r.first_bad_wg, r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor,
-      r.cus_covered, r.simds_covered, r.xccs_covered, r.xccs_per_tile_min, r.fill_us, r.kernel_us, r.drain_us, r.verify_us,
-      r.total_us, r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id, json_escape(r.pci_bus_id).c_str(),
+      r.simds_covered, r.xccs_covered, x.after_coverage.c_str(), r.kernel_us, x.after_kernel_us.c_str(), r.total_us,
+      r.in_flight_s, r.kept_queue ? "true" : "false", r.kfd_node_id, json_escape(r.pci_bus_id).c_str(),
       json_escape(r.error).c_str());
 }
 
-// the fused attention check's line: the GEMM check's fields with four stages (K feed, V feed, m / l words, O words), the
-// head and block counts, the fill's GPU time and the count of inexact v_exp_f32 results
-inline std::string datapath_attn_json(const mi355x_datapath_attn_result& r) {
-  return json_format(
-      "{\"ordinal\":%d,\"ok\":%s,\"hsa_error\":%d,\"nonce\":%u,\"grid\":%d,\"heads\":%d,\"qblocks\":%d,\"kblocks\":%d,"
-      "\"cu_count\":%d,\"num_xcc\":%d,\"records_ok\":%d,\"mfma_bad\":%u,\"stage_bad\":[%u,%u,%u,%u],\"tile_bad\":%u,"
-      "\"exp_inexact\":%u,\"first_bad_wg\":%d,\"first_bad_stage\":%d,\"first_bad_word\":%d,\"first_bad_got\":%u,"
-      "\"first_bad_want\":%u,\"first_bad_xor\":%u,\"cus_covered\":%d,\"simds_covered\":%d,\"xccs_covered\":%d,"
-      "\"fill_us\":%.2f,\"kernel_us\":%.2f,\"verify_us\":%.1f,\"total_us\":%.1f,"
-      "\"in_flight_s\":%.2f,\"kept_queue\":%s,\"kfd_node_id\":%d,\"pci_bus_id\":\"%s\",\"error\":\"%s\"}",
-      r.ordinal, r.ok ? "true" : "false", r.hsa_error, r.nonce, r.grid, r.heads, r.qblocks, r.kblocks, r.cu_count, r.num_xcc,
-      r.records_ok, r.mfma_bad, r.stage_bad[0], r.stage_bad[1], r.stage_bad[2], r.stage_bad[3], r.tile_bad, r.exp_inexact,
-      r.first_bad_wg, r.first_bad_stage, r.first_bad_word, r.first_bad_got, r.first_bad_want, r.first_bad_xor,
-      r.cus_covered, r.simds_covered, r.xccs_covered, r.fill_us, r.kernel_us, r.verify_us, r.total_us, r.in_flight_s,
-      r.kept_queue ? "true" : "false", r.kfd_node_id, json_escape(r.pci_bus_id).c_str(), json_escape(r.error).c_str());
-}
+// the kinds' named printers (the bf16 result is the int8 check's, liveness_probe.h)
+inline std::string datapath_json(const mi355x_datapath_result& r) { return datapath_device_json(r); }
+inline std::string datapath_i8_json(const mi355x_datapath_i8_result& r) { return datapath_device_json(r); }
+inline std::string datapath_bf16_json(const mi355x_datapath_bf16_result& r) { return datapath_device_json(r); }
+inline std::string datapath_fp8_json(const mi355x_datapath_fp8_result& r) { return datapath_device_json(r); }
+inline std::string datapath_f16_json(const mi355x_datapath_f16_result& r) { return datapath_device_json(r); }
+inline std::string datapath_f64_json(const mi355x_datapath_f64_result& r) { return datapath_device_json(r); }
+inline std::string datapath_f6f4_json(const mi355x_datapath_f6f4_result& r) { return datapath_device_json(r); }
+inline std::string datapath_sparse_json(const mi355x_datapath_sparse_result& r) { return datapath_device_json(r); }
+inline std::string datapath_gemm_json(const mi355x_datapath_gemm_result& r) { return datapath_device_json(r); }
+inline std::string datapath_splitk_json(const mi355x_datapath_splitk_result& r) { return datapath_device_json(r); }
+inline std::string datapath_attn_json(const mi355x_datapath_attn_result& r) { return datapath_device_json(r); }
 
 // phase_us of one device: HSA build = code object, queue, buffers, dispatch;
 // HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch
@@ -331,17 +224,8 @@ inline std::string serve_reply_json(bool tagged, unsigned long long id, const st
       "{%s\"ok\":%s,\"hip_device_count\":%d,\"sweep\":%s,\"perf\":%s,\"t_ready_ns\":%llu,", id_field(tagged, id).c_str(),
       ok ? "true" : "false", n, kind == "sweep" ? "true" : "false", kind == "perf" ? "true" : "false",
       static_cast<unsigned long long>(t_ready_ns));
-  const char* key = kind == "datapath" ? "\"datapath\":true," : kind == "datapath_i8"   ? "\"datapath_i8\":true,"
-                    : kind == "datapath_bf16" ? "\"datapath_bf16\":true,"
-                    : kind == "datapath_fp8"  ? "\"datapath_fp8\":true,"
-                    : kind == "datapath_f16"  ? "\"datapath_f16\":true,"
-                    : kind == "datapath_f64"  ? "\"datapath_f64\":true,"
-                    : kind == "datapath_f6f4" ? "\"datapath_f6f4\":true,"
-                    : kind == "datapath_sparse" ? "\"datapath_sparse\":true,"
-                    : kind == "datapath_gemm" ? "\"datapath_gemm\":true,"
-                    : kind == "datapath_splitk" ? "\"datapath_splitk\":true,"
-                    : kind == "datapath_attn" ? "\"datapath_attn\":true,"
-                                              : "";
+  const int dp = probe_kind_index(kind);
+  const std::string key = dp < 0 ? "" : std::string("\"") + kProbeKinds[dp].wire + "\":true,";
   return head + key + "\"devices\":" + devices + "}";
 }
 
@@ -359,8 +243,7 @@ inline std::string runtime_init_failed_json(int code, uint64_t t_start_ns, const
       code, static_cast<unsigned long long>(t_start_ns), init_profile.c_str());
 }
 
-// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16 / --datapath-f64 /
-// --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk / --datapath-attn
+// --sweep / --perf / a datapath kind's flag (probe_kinds.h)
 inline std::string oneshot_check_json(const std::string& kind, bool ok, int n, uint64_t t_start_ns,
                                       uint64_t t_runtime_ns, uint64_t t_ready_ns, const std::string& devices) {
   return json_format(

@@ -46,6 +46,7 @@
 #include <unistd.h>
 #include <time.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -61,6 +62,7 @@
 #include "liveness_kernel.h"
 #include "mi355x/liveness_probe.h"
 #include "probe_json.h"
+#include "probe_kinds.h"
 #include "probe_request.h"
 
 // defined by the container-emulation builds (native/tools/probe_emu.cpp) only
@@ -95,17 +97,6 @@ uint64_t mono_ns() {
 }
 
 using mi355x::blank_result;
-using mi355x::datapath_bf16_json;
-using mi355x::datapath_fp8_json;
-using mi355x::datapath_f16_json;
-using mi355x::datapath_f64_json;
-using mi355x::datapath_f6f4_json;
-using mi355x::datapath_sparse_json;
-using mi355x::datapath_gemm_json;
-using mi355x::datapath_splitk_json;
-using mi355x::datapath_attn_json;
-using mi355x::datapath_i8_json;
-using mi355x::datapath_json;
 using mi355x::json_escape;
 using mi355x::parse_request;
 using mi355x::perf_json;
@@ -136,72 +127,6 @@ int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double timeout_
   return mi355x_hsa_perf_check(o, nonce, bytes, iters, timeout_s, r);
 }
 void perf_poison(uint64_t unit) { mi355x_hsa_perf_poison(unit); }
-int datapath_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_result* r) {
-  return mi355x_hsa_datapath_check(o, nonce, timeout_s, r);
-}
-void datapath_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_corrupt(stage, word, bit, ordinal);
-}
-int datapath_i8_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_i8_result* r) {
-  return mi355x_hsa_datapath_i8_check(o, nonce, timeout_s, r);
-}
-void datapath_i8_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_i8_corrupt(stage, word, bit, ordinal);
-}
-int datapath_bf16_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_bf16_result* r) {
-  return mi355x_hsa_datapath_bf16_check(o, nonce, timeout_s, r);
-}
-void datapath_bf16_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_bf16_corrupt(stage, word, bit, ordinal);
-}
-int datapath_fp8_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_fp8_result* r) {
-  return mi355x_hsa_datapath_fp8_check(o, nonce, timeout_s, r);
-}
-void datapath_fp8_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_fp8_corrupt(stage, word, bit, ordinal);
-}
-int datapath_f16_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_f16_result* r) {
-  return mi355x_hsa_datapath_f16_check(o, nonce, timeout_s, r);
-}
-void datapath_f16_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_f16_corrupt(stage, word, bit, ordinal);
-}
-int datapath_f64_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_f64_result* r) {
-  return mi355x_hsa_datapath_f64_check(o, nonce, timeout_s, r);
-}
-void datapath_f64_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_f64_corrupt(stage, word, bit, ordinal);
-}
-int datapath_f6f4_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_f6f4_result* r) {
-  return mi355x_hsa_datapath_f6f4_check(o, nonce, timeout_s, r);
-}
-void datapath_f6f4_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_f6f4_corrupt(stage, word, bit, ordinal);
-}
-int datapath_sparse_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_sparse_result* r) {
-  return mi355x_hsa_datapath_sparse_check(o, nonce, timeout_s, r);
-}
-void datapath_sparse_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_sparse_corrupt(stage, word, bit, ordinal);
-}
-int datapath_gemm_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_gemm_result* r) {
-  return mi355x_hsa_datapath_gemm_check(o, nonce, timeout_s, r);
-}
-void datapath_gemm_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_gemm_corrupt(stage, word, bit, ordinal);
-}
-int datapath_splitk_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_splitk_result* r) {
-  return mi355x_hsa_datapath_splitk_check(o, nonce, timeout_s, r);
-}
-void datapath_splitk_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_splitk_corrupt(stage, word, bit, ordinal);
-}
-int datapath_attn_check(int o, uint32_t nonce, double timeout_s, mi355x_datapath_attn_result* r) {
-  return mi355x_hsa_datapath_attn_check(o, nonce, timeout_s, r);
-}
-void datapath_attn_corrupt(int stage, int word, int bit, int ordinal) {
-  mi355x_hsa_datapath_attn_corrupt(stage, word, bit, ordinal);
-}
 void init_phases(double out[5]) { mi355x_hsa_init_phases(out); }
 void defer_teardown() { mi355x_hsa_probe_defer_release(1); }
 void teardown() { mi355x_hsa_probe_release(); }
@@ -235,50 +160,6 @@ int chip_sweep(int o, uint32_t nonce, int iters, double, mi355x_sweep_result* r)
   return needs_hsa_build("--sweep", blank, r);
 }
 void perf_poison(uint64_t) {}
-void datapath_corrupt(int, int, int, int) {}
-int datapath_check(int o, uint32_t nonce, double, mi355x_datapath_result* r) {
-  return needs_hsa_build("--datapath", blank_result<mi355x_datapath_result>(o, nonce), r);
-}
-void datapath_i8_corrupt(int, int, int, int) {}
-int datapath_i8_check(int o, uint32_t nonce, double, mi355x_datapath_i8_result* r) {
-  return needs_hsa_build("--datapath-i8", blank_result<mi355x_datapath_i8_result>(o, nonce), r);
-}
-void datapath_bf16_corrupt(int, int, int, int) {}
-int datapath_bf16_check(int o, uint32_t nonce, double, mi355x_datapath_bf16_result* r) {
-  return needs_hsa_build("--datapath-bf16", blank_result<mi355x_datapath_bf16_result>(o, nonce), r);
-}
-void datapath_fp8_corrupt(int, int, int, int) {}
-int datapath_fp8_check(int o, uint32_t nonce, double, mi355x_datapath_fp8_result* r) {
-  return needs_hsa_build("--datapath-fp8", blank_result<mi355x_datapath_fp8_result>(o, nonce), r);
-}
-void datapath_f16_corrupt(int, int, int, int) {}
-int datapath_f16_check(int o, uint32_t nonce, double, mi355x_datapath_f16_result* r) {
-  return needs_hsa_build("--datapath-f16", blank_result<mi355x_datapath_f16_result>(o, nonce), r);
-}
-void datapath_f64_corrupt(int, int, int, int) {}
-int datapath_f64_check(int o, uint32_t nonce, double, mi355x_datapath_f64_result* r) {
-  return needs_hsa_build("--datapath-f64", blank_result<mi355x_datapath_f64_result>(o, nonce), r);
-}
-void datapath_f6f4_corrupt(int, int, int, int) {}
-int datapath_f6f4_check(int o, uint32_t nonce, double, mi355x_datapath_f6f4_result* r) {
-  return needs_hsa_build("--datapath-f6f4", blank_result<mi355x_datapath_f6f4_result>(o, nonce), r);
-}
-void datapath_sparse_corrupt(int, int, int, int) {}
-int datapath_sparse_check(int o, uint32_t nonce, double, mi355x_datapath_sparse_result* r) {
-  return needs_hsa_build("--datapath-sparse", blank_result<mi355x_datapath_sparse_result>(o, nonce), r);
-}
-void datapath_gemm_corrupt(int, int, int, int) {}
-int datapath_gemm_check(int o, uint32_t nonce, double, mi355x_datapath_gemm_result* r) {
-  return needs_hsa_build("--datapath-gemm", blank_result<mi355x_datapath_gemm_result>(o, nonce), r);
-}
-void datapath_splitk_corrupt(int, int, int, int) {}
-int datapath_splitk_check(int o, uint32_t nonce, double, mi355x_datapath_splitk_result* r) {
-  return needs_hsa_build("--datapath-splitk", blank_result<mi355x_datapath_splitk_result>(o, nonce), r);
-}
-void datapath_attn_corrupt(int, int, int, int) {}
-int datapath_attn_check(int o, uint32_t nonce, double, mi355x_datapath_attn_result* r) {
-  return needs_hsa_build("--datapath-attn", blank_result<mi355x_datapath_attn_result>(o, nonce), r);
-}
 int perf_check(int o, uint32_t nonce, uint64_t bytes, int iters, double, mi355x_perf_result* r) {
   auto blank = blank_result<mi355x_perf_result>(o, nonce);
   blank.bytes = bytes;
@@ -433,9 +314,58 @@ bool run_on_each(const std::vector<int>& ords, const std::vector<uint32_t>& nonc
   return ok;
 }
 
-// --sweep / --perf / --datapath / --datapath-i8 / --datapath-bf16 / --datapath-fp8 / --datapath-f16 /
-// --datapath-f64 / --datapath-f6f4 / --datapath-sparse / --datapath-gemm / --datapath-splitk / --datapath-attn and the server's requests
-// of those kinds.
+// What the probe does for a datapath kind (a row of probe_kinds.h): `run` is
+// the check on each device of a request, `corrupt` its fault injection. The
+// HSA build forwards to the kind's mi355x_hsa_* pair; the HIP build has none of
+// the checks and answers each device that the kind's flag needs the other build.
+using CorruptDatapath = void (*)(int stage, int word, int bit, int ordinal);
+struct DatapathOps {
+  const char* kind;
+  bool (*run)(const mi355x::ProbeKind& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces,
+              const std::vector<double>& timeouts, int n, std::string& json);
+  CorruptDatapath corrupt;
+};
+#ifdef MI355X_PROBE_HSA
+template <typename R, int (*Check)(int, uint32_t, double, R*), std::string (*ToJson)(const R&)>
+bool run_datapath(const mi355x::ProbeKind&, const std::vector<int>& ords, const std::vector<uint32_t>& nonces,
+                  const std::vector<double>& timeouts, int n, std::string& json) {
+  return run_on_each<R>(ords, nonces, timeouts, n, Check, ToJson, json);
+}
+#define MI355X_DATAPATH_OPS(kind)                                                                       \
+  {#kind, run_datapath<mi355x_##kind##_result, mi355x_hsa_##kind##_check, mi355x::kind##_json>,         \
+   mi355x_hsa_##kind##_corrupt}
+#else
+template <typename R, std::string (*ToJson)(const R&)>
+bool run_datapath(const mi355x::ProbeKind& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces,
+                  const std::vector<double>& timeouts, int n, std::string& json) {
+  const std::string flag = mi355x::probe_kind_flag(kind);
+  return run_on_each<R>(ords, nonces, timeouts, n, [&](int o, uint32_t nonce, double, R* r) {
+    return needs_hsa_build(flag.c_str(), blank_result<R>(o, nonce), r);
+  }, ToJson, json);
+}
+#define MI355X_DATAPATH_OPS(kind) \
+  {#kind, run_datapath<mi355x_##kind##_result, mi355x::kind##_json>, [](int, int, int, int) {}}
+#endif
+constexpr DatapathOps kDatapathOps[] = {
+    MI355X_DATAPATH_OPS(datapath),        MI355X_DATAPATH_OPS(datapath_i8),     MI355X_DATAPATH_OPS(datapath_bf16),
+    MI355X_DATAPATH_OPS(datapath_fp8),    MI355X_DATAPATH_OPS(datapath_f16),    MI355X_DATAPATH_OPS(datapath_f64),
+    MI355X_DATAPATH_OPS(datapath_f6f4),   MI355X_DATAPATH_OPS(datapath_sparse), MI355X_DATAPATH_OPS(datapath_gemm),
+    MI355X_DATAPATH_OPS(datapath_splitk), MI355X_DATAPATH_OPS(datapath_attn),
+};
+#undef MI355X_DATAPATH_OPS
+// kDatapathOps[i] belongs to kProbeKinds[i]
+constexpr bool datapath_ops_follow_the_kinds() {
+  if (sizeof(kDatapathOps) / sizeof(kDatapathOps[0]) != mi355x::kProbeKindCount) return false;
+  for (int i = 0; i < mi355x::kProbeKindCount; ++i) {
+    const char *a = kDatapathOps[i].kind, *b = mi355x::kProbeKinds[i].wire;
+    while (*a && *a == *b) ++a, ++b;
+    if (*a != *b) return false;
+  }
+  return true;
+}
+static_assert(datapath_ops_follow_the_kinds(), "one entry per row of probe_kinds.h, in its order");
+
+// --sweep / --perf / a datapath kind's flag and the server's requests of those kinds.
 // `iters`: the sweep's tile iterations or the throughput check's MFMA
 // iterations; `bytes`: the throughput check's HBM buffer.
 bool run_check(const std::string& kind, const std::vector<int>& ords, const std::vector<uint32_t>& nonces, int iters,
@@ -448,57 +378,24 @@ bool run_check(const std::string& kind, const std::vector<int>& ords, const std:
     return run_on_each(ords, nonces, timeouts, n, [=](int o, uint32_t nonce, double t, mi355x_perf_result* r) {
       return perf_check(o, nonce, bytes, iters, t, r);
     }, perf_json, json);
-  if (kind == "datapath_i8")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_i8_result* r) {
-      return datapath_i8_check(o, nonce, t, r);
-    }, datapath_i8_json, json);
-  if (kind == "datapath_bf16")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_bf16_result* r) {
-      return datapath_bf16_check(o, nonce, t, r);
-    }, datapath_bf16_json, json);
-  if (kind == "datapath_fp8")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_fp8_result* r) {
-      return datapath_fp8_check(o, nonce, t, r);
-    }, datapath_fp8_json, json);
-  if (kind == "datapath_f16")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_f16_result* r) {
-      return datapath_f16_check(o, nonce, t, r);
-    }, datapath_f16_json, json);
-  if (kind == "datapath_f64")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_f64_result* r) {
-      return datapath_f64_check(o, nonce, t, r);
-    }, datapath_f64_json, json);
-  if (kind == "datapath_f6f4")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_f6f4_result* r) {
-      return datapath_f6f4_check(o, nonce, t, r);
-    }, datapath_f6f4_json, json);
-  if (kind == "datapath_sparse")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_sparse_result* r) {
-      return datapath_sparse_check(o, nonce, t, r);
-    }, datapath_sparse_json, json);
-  if (kind == "datapath_gemm")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_gemm_result* r) {
-      return datapath_gemm_check(o, nonce, t, r);
-    }, datapath_gemm_json, json);
-  if (kind == "datapath_splitk")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_splitk_result* r) {
-      return datapath_splitk_check(o, nonce, t, r);
-    }, datapath_splitk_json, json);
-  if (kind == "datapath_attn")
-    return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_attn_result* r) {
-      return datapath_attn_check(o, nonce, t, r);
-    }, datapath_attn_json, json);
-  return run_on_each(ords, nonces, timeouts, n, [](int o, uint32_t nonce, double t, mi355x_datapath_result* r) {
-    return datapath_check(o, nonce, t, r);
-  }, datapath_json, json);
+  const int dp = mi355x::probe_kind_index(kind);
+  if (dp < 0) return json = "[]", false;  // parse_request and main() name no other kind
+  return kDatapathOps[dp].run(mi355x::kProbeKinds[dp], ords, nonces, timeouts, n, json);
 }
 
-// "S:W:B" or "S:W:B@O" of --corrupt-datapath and of its -i8, -bf16, -fp8, -f16, -f64, -f6f4, -sparse, -gemm, -splitk and -attn siblings
+// "S:W:B" or "S:W:B@O" of --corrupt-datapath and its siblings (probe_kinds.h)
 bool parse_corrupt_datapath(const char* spec, int out[4]) {
   out[3] = -1;
   char tail = 0;
   const int n = std::sscanf(spec, "%d:%d:%d@%d%c", &out[0], &out[1], &out[2], &out[3], &tail);
   return n == 3 || n == 4;
+}
+
+// the row of probe_kinds.h whose suffix makes `stem` the flag `a`, or -1
+int kind_of_flag(const std::string& a, const char* stem) {
+  for (int i = 0; i < mi355x::kProbeKindCount; ++i)
+    if (a == std::string(stem) + mi355x::kProbeKinds[i].suffix) return i;
+  return -1;
 }
 
 std::string devices_json(const std::vector<mi355x_probe_result>& results) {
@@ -515,17 +412,7 @@ std::string devices_json(const std::vector<mi355x_probe_result>& results) {
 //     [@<id> ]probe <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]sweep <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]perf <mfma_iters> <timeout_s> <mib> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_bf16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_fp8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_f16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_f64 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_f6f4 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_sparse <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_gemm <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_splitk <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_attn <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]<datapath kind> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...   (probe_kinds.h)
 // is answered with one JSON line {"id":..,"ok":..,"t_ready_ns":..,"devices":[..]}
 // ("id" only for a tagged request). A device's own deadline replaces the
 // request's timeout for that device: the plugin gives GPUs that run other
@@ -679,17 +566,7 @@ int main(int argc, char** argv) {
   bool peer_mode = false;
   bool sweep_mode = false;
   bool perf_mode = false;
-  bool datapath_mode = false;
-  bool datapath_i8_mode = false;
-  bool datapath_bf16_mode = false;
-  bool datapath_fp8_mode = false;
-  bool datapath_f16_mode = false;
-  bool datapath_f64_mode = false;
-  bool datapath_f6f4_mode = false;
-  bool datapath_sparse_mode = false;
-  bool datapath_gemm_mode = false;
-  bool datapath_splitk_mode = false;
-  bool datapath_attn_mode = false;
+  int datapath_mode = -1;  // a row of probe_kinds.h; of several kind flags the first row's wins, wherever it stands
   uint64_t perf_mib = 4096;
   int perf_iters = 1 << 16;
   uint64_t peer_bytes = 64ull << 20;
@@ -731,105 +608,15 @@ int main(int argc, char** argv) {
       sweep_mode = true;
     } else if (a == "--perf") {
       perf_mode = true;
-    } else if (a == "--datapath") {
-      datapath_mode = true;
-    } else if (a == "--corrupt-datapath") {
+    } else if (const int k = kind_of_flag(a, "--datapath"); k >= 0) {
+      datapath_mode = datapath_mode < 0 ? k : std::min(datapath_mode, k);
+    } else if (const int k = kind_of_flag(a, "--corrupt-datapath"); k >= 0) {
       int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath must be STAGE:WORD:BIT[@ORDINAL]\n");
+      if (!parse_corrupt_datapath(next(a.c_str()), c)) {
+        std::fprintf(stderr, "%s must be STAGE:WORD:BIT[@ORDINAL]\n", a.c_str());
         return 2;
       }
-      datapath_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-i8") {
-      datapath_i8_mode = true;
-    } else if (a == "--corrupt-datapath-i8") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-i8"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-i8 must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_i8_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-bf16") {
-      datapath_bf16_mode = true;
-    } else if (a == "--corrupt-datapath-bf16") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-bf16"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-bf16 must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_bf16_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-fp8") {
-      datapath_fp8_mode = true;
-    } else if (a == "--corrupt-datapath-fp8") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-fp8"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-fp8 must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_fp8_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-f16") {
-      datapath_f16_mode = true;
-    } else if (a == "--corrupt-datapath-f16") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-f16"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-f16 must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_f16_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-f64") {
-      datapath_f64_mode = true;
-    } else if (a == "--corrupt-datapath-f64") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-f64"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-f64 must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_f64_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-f6f4") {
-      datapath_f6f4_mode = true;
-    } else if (a == "--corrupt-datapath-f6f4") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-f6f4"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-f6f4 must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_f6f4_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-sparse") {
-      datapath_sparse_mode = true;
-    } else if (a == "--corrupt-datapath-sparse") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-sparse"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-sparse must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_sparse_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-gemm") {
-      datapath_gemm_mode = true;
-    } else if (a == "--corrupt-datapath-gemm") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-gemm"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-gemm must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_gemm_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-splitk") {
-      datapath_splitk_mode = true;
-    } else if (a == "--corrupt-datapath-splitk") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-splitk"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-splitk must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_splitk_corrupt(c[0], c[1], c[2], c[3]);
-    } else if (a == "--datapath-attn") {
-      datapath_attn_mode = true;
-    } else if (a == "--corrupt-datapath-attn") {
-      int c[4];
-      if (!parse_corrupt_datapath(next("--corrupt-datapath-attn"), c)) {
-        std::fprintf(stderr, "--corrupt-datapath-attn must be STAGE:WORD:BIT[@ORDINAL]\n");
-        return 2;
-      }
-      datapath_attn_corrupt(c[0], c[1], c[2], c[3]);
+      kDatapathOps[k].corrupt(c[0], c[1], c[2], c[3]);
     } else if (a == "--perf-mib") {
       perf_mib = std::strtoull(next("--perf-mib"), nullptr, 0);
     } else if (a == "--perf-iters") {
@@ -850,21 +637,14 @@ int main(int argc, char** argv) {
     } else if (a == "--peer-reps") {
       peer_reps = std::atoi(next("--peer-reps"));
     } else if (a == "-h" || a == "--help") {
+      std::string datapath_flags;
+      for (const mi355x::ProbeKind& k : mi355x::kProbeKinds)
+        datapath_flags += "[" + mi355x::probe_kind_flag(k) + " [" + mi355x::probe_kind_corrupt_flag(k) + " S:W:B[@ORDINAL]]] ";
       std::printf("usage: %s [--devices all|0,1,..] [--nonce N] [--iters N] [--identify] [--timeout S] "
                   "[--sample-init PERIOD_US] [--exit shutdown|release|fast] [--serve [--keep]] [--peer [--peer-bytes B] [--peer-reps R]] [--sweep] "
-                  "[--perf [--perf-mib M] [--perf-iters N] [--poison-hbm UNIT]] [--datapath [--corrupt-datapath S:W:B[@ORDINAL]]] "
-                  "[--datapath-i8 [--corrupt-datapath-i8 S:W:B[@ORDINAL]]] "
-                  "[--datapath-bf16 [--corrupt-datapath-bf16 S:W:B[@ORDINAL]]] "
-                  "[--datapath-fp8 [--corrupt-datapath-fp8 S:W:B[@ORDINAL]]] "
-                  "[--datapath-f16 [--corrupt-datapath-f16 S:W:B[@ORDINAL]]] "
-                  "[--datapath-f64 [--corrupt-datapath-f64 S:W:B[@ORDINAL]]] "
-                  "[--datapath-f6f4 [--corrupt-datapath-f6f4 S:W:B[@ORDINAL]]] "
-                  "[--datapath-sparse [--corrupt-datapath-sparse S:W:B[@ORDINAL]]] "
-                  "[--datapath-gemm [--corrupt-datapath-gemm S:W:B[@ORDINAL]]] "
-                  "[--datapath-splitk [--corrupt-datapath-splitk S:W:B[@ORDINAL]]] "
-                  "[--datapath-attn [--corrupt-datapath-attn S:W:B[@ORDINAL]]] "
+                  "[--perf [--perf-mib M] [--perf-iters N] [--poison-hbm UNIT]] %s"
                   "[--corrupt-word K[@ORDINAL]] [--hip-stream own|null]\n",
-                  argv[0]);
+                  argv[0], datapath_flags.c_str());
       return 0;
     } else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -911,15 +691,8 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> nonces;
   for (size_t i = 0; i < ords.size(); ++i) nonces.push_back(nonce + static_cast<uint32_t>(i));
   const std::vector<double> timeouts(ords.size(), timeout_s);
-  if (perf_mode || datapath_mode || datapath_i8_mode || datapath_bf16_mode || datapath_fp8_mode ||
-      datapath_f16_mode || datapath_f64_mode || datapath_f6f4_mode || datapath_sparse_mode || datapath_gemm_mode ||
-      datapath_splitk_mode || datapath_attn_mode || sweep_mode) {
-    const char* kind = perf_mode ? "perf" : datapath_mode ? "datapath" : datapath_i8_mode ? "datapath_i8"
-                       : datapath_bf16_mode ? "datapath_bf16" : datapath_fp8_mode ? "datapath_fp8"
-                       : datapath_f16_mode ? "datapath_f16" : datapath_f64_mode ? "datapath_f64"
-                       : datapath_f6f4_mode ? "datapath_f6f4" : datapath_sparse_mode ? "datapath_sparse"
-                       : datapath_gemm_mode ? "datapath_gemm" : datapath_splitk_mode ? "datapath_splitk"
-                       : datapath_attn_mode ? "datapath_attn" : "sweep";
+  if (perf_mode || datapath_mode >= 0 || sweep_mode) {
+    const char* kind = perf_mode ? "perf" : datapath_mode >= 0 ? mi355x::kProbeKinds[datapath_mode].wire : "sweep";
     std::string body;
     const bool ok = run_check(kind, ords, nonces, perf_mode ? perf_iters : iters, perf_mib << 20, timeouts, n, body);
     std::printf("%s\n", mi355x::oneshot_check_json(kind, ok, n, t_start, t_runtime, mono_ns(), body).c_str());

@@ -4,17 +4,7 @@
 //     [@<id> ]probe <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]sweep <iters> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
 //     [@<id> ]perf <mfma_iters> <timeout_s> <mib> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_i8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_bf16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_fp8 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_f16 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_f64 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_f6f4 <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_sparse <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_gemm <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_splitk <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
-//     [@<id> ]datapath_attn <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...
+//     [@<id> ]<datapath kind> <timeout_s> <ordinal>:<nonce>[:<deadline_s>] ...   (a row of probe_kinds.h)
 // A device's own deadline (> 0) replaces the request's timeout for that device.
 #pragma once
 
@@ -25,14 +15,14 @@
 #include <string>
 #include <vector>
 
+#include "probe_kinds.h"
+
 namespace mi355x {
 
 struct ServeRequest {
   bool tagged = false;
   unsigned long long id = 0;
-  std::string kind;  // probe | sweep | perf | datapath | datapath_i8 | datapath_bf16 | datapath_fp8 | datapath_f16 |
-                     // datapath_f64 | datapath_f6f4 | datapath_sparse | datapath_gemm | datapath_splitk |
-                     // datapath_attn
+  std::string kind;  // probe | sweep | perf | a datapath kind of probe_kinds.h
   int iters = 0;
   double timeout_s = 0;
   unsigned long long perf_mib = 0;
@@ -63,42 +53,16 @@ inline bool parse_request(const std::string& line, ServeRequest* r) {
   }
   int consumed = 0;
   bool parsed = false;
-  if (std::strncmp(p, "perf ", 5) == 0) {
+  // the whole verb, up to its blank: the order of the table's rows does not matter
+  const char* const blank = std::strchr(p, ' ');
+  const int dp = blank ? probe_kind_index(p, static_cast<size_t>(blank - p)) : -1;
+  if (dp >= 0) {
+    r->kind = kProbeKinds[dp].wire;
+    parsed = std::sscanf(blank, " %lf %n", &r->timeout_s, &consumed) >= 1;
+    if (parsed && consumed) consumed += static_cast<int>(blank - p);
+  } else if (std::strncmp(p, "perf ", 5) == 0) {
     r->kind = "perf";
     parsed = std::sscanf(p, "perf %d %lf %llu %n", &r->iters, &r->timeout_s, &r->perf_mib, &consumed) >= 3;
-  } else if (std::strncmp(p, "datapath_i8 ", 12) == 0) {
-    r->kind = "datapath_i8";
-    parsed = std::sscanf(p, "datapath_i8 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_bf16 ", 14) == 0) {
-    r->kind = "datapath_bf16";
-    parsed = std::sscanf(p, "datapath_bf16 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_fp8 ", 13) == 0) {
-    r->kind = "datapath_fp8";
-    parsed = std::sscanf(p, "datapath_fp8 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_f16 ", 13) == 0) {
-    r->kind = "datapath_f16";
-    parsed = std::sscanf(p, "datapath_f16 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_f64 ", 13) == 0) {
-    r->kind = "datapath_f64";
-    parsed = std::sscanf(p, "datapath_f64 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_f6f4 ", 14) == 0) {
-    r->kind = "datapath_f6f4";
-    parsed = std::sscanf(p, "datapath_f6f4 %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_sparse ", 16) == 0) {
-    r->kind = "datapath_sparse";
-    parsed = std::sscanf(p, "datapath_sparse %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_gemm ", 14) == 0) {
-    r->kind = "datapath_gemm";
-    parsed = std::sscanf(p, "datapath_gemm %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_splitk ", 16) == 0) {
-    r->kind = "datapath_splitk";
-    parsed = std::sscanf(p, "datapath_splitk %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath_attn ", 14) == 0) {
-    r->kind = "datapath_attn";
-    parsed = std::sscanf(p, "datapath_attn %lf %n", &r->timeout_s, &consumed) >= 1;
-  } else if (std::strncmp(p, "datapath ", 9) == 0) {
-    r->kind = "datapath";
-    parsed = std::sscanf(p, "datapath %lf %n", &r->timeout_s, &consumed) >= 1;
   } else if (std::strncmp(p, "sweep ", 6) == 0) {
     r->kind = "sweep";
     parsed = std::sscanf(p, "sweep %d %lf %n", &r->iters, &r->timeout_s, &consumed) >= 2;

@@ -16,6 +16,8 @@
 //        a document of its own (tests/test_probe_contract_bf16.py): `replies` stays as recorded
 //   probe_contract_cli replies-fp8    the same for the datapath_fp8 kind (tests/test_probe_contract_fp8.py)
 //   probe_contract_cli replies-f16    the same for the datapath_f16 kind (tests/test_probe_contract_f16.py)
+//   probe_contract_cli replies-rest   the same for the datapath_f64, _f6f4, _sparse, _gemm, _splitk and _attn kinds, in
+//        one document (tests/test_probe_contract_rest.py); the fields only those kinds have are filled too
 //   probe_contract_cli parse < lines  per request line one JSON line: the parsed request
 //        {"tagged","id","kind","iters","timeout","mib","devices":[[ordinal,nonce,deadline],..]},
 //        or "bad request" for a line the server refuses
@@ -251,6 +253,68 @@ int cmd_replies_f16() {
   return 0;
 }
 
+// the fields only the GEMM, split-K and attention results have: distinct, non-zero, clear of filled_datapath's
+void fill_extras(mi355x_datapath_gemm_result* r, Counter& c) {
+  r->ksteps = c.i();
+  r->fill_us = c.d();
+  r->verify_us = c.d();
+}
+void fill_extras(mi355x_datapath_splitk_result* r, Counter& c) {
+  r->tiles = c.i();
+  r->splits = c.i();
+  r->ksteps = c.i();
+  r->ledger_bad = c.u();
+  r->xccs_per_tile_min = c.i();
+  r->fill_us = c.d();
+  r->drain_us = c.d();
+  r->verify_us = c.d();
+}
+void fill_extras(mi355x_datapath_attn_result* r, Counter& c) {
+  r->heads = c.i();
+  r->qblocks = c.i();
+  r->kblocks = c.i();
+  r->exp_inexact = c.u();
+  r->fill_us = c.d();
+  r->verify_us = c.d();
+}
+template <typename R>
+void fill_extras(R*, Counter&) {}
+
+template <typename R>
+std::string three_of(std::string (*to_json)(const R&)) {
+  R f8 = filled_datapath<R>(8), f16 = filled_datapath<R>(16);
+  Counter c8, c16;
+  c8.n = c16.n = 200;
+  fill_extras(&f8, c8);
+  fill_extras(&f16, c16);
+  return three(to_json(blank_result<R>(0, 0)), to_json(f8), to_json(f16));
+}
+
+int cmd_replies_rest() {
+  const uint64_t t0 = 1000000001ull, t1 = 1000000002ull, t2 = 1000000003ull;
+  const char* const kinds[] = {"datapath_f64",  "datapath_f6f4",   "datapath_sparse",
+                               "datapath_gemm", "datapath_splitk", "datapath_attn"};
+  std::string o = "{\n\"devices\":{";
+  o += "\n\"datapath_f64\":" + three_of<mi355x_datapath_f64_result>(datapath_f64_json);
+  o += ",\n\"datapath_f6f4\":" + three_of<mi355x_datapath_f6f4_result>(datapath_f6f4_json);
+  o += ",\n\"datapath_sparse\":" + three_of<mi355x_datapath_sparse_result>(datapath_sparse_json);
+  o += ",\n\"datapath_gemm\":" + three_of<mi355x_datapath_gemm_result>(datapath_gemm_json);
+  o += ",\n\"datapath_splitk\":" + three_of<mi355x_datapath_splitk_result>(datapath_splitk_json);
+  o += ",\n\"datapath_attn\":" + three_of<mi355x_datapath_attn_result>(datapath_attn_json);
+  o += "},\n\"serve\":{";
+  for (const char* kind : kinds)
+    o += std::string(kind == kinds[0] ? "" : ",") + "\n\"" + kind + "\":{\"untagged\":" +
+         serve_reply_json(false, 0, kind, true, 8, t2, "[]") + ",\n\"tagged\":" +
+         serve_reply_json(true, 5, kind, false, 8, t2, "[]") + "}";
+  o += "},\n\"oneshot\":{";
+  for (const char* kind : kinds)
+    o += std::string(kind == kinds[0] ? "" : ",") + "\n\"" + kind + "\":" +
+         oneshot_check_json(kind, true, 8, t0, t1, t2, "[]");
+  o += "}\n}\n";
+  std::fputs(o.c_str(), stdout);
+  return 0;
+}
+
 int cmd_parse() {
   char buf[8192];  // the server's own line buffer
   while (std::fgets(buf, sizeof(buf), stdin)) {
@@ -278,7 +342,8 @@ int main(int argc, char** argv) {
   if (cmd == "replies-bf16") return cmd_replies_bf16();
   if (cmd == "replies-fp8") return cmd_replies_fp8();
   if (cmd == "replies-f16") return cmd_replies_f16();
+  if (cmd == "replies-rest") return cmd_replies_rest();
   if (cmd == "parse") return cmd_parse();
-  std::fprintf(stderr, "usage: %s replies|replies-bf16|replies-fp8|replies-f16|parse\n", argv[0]);
+  std::fprintf(stderr, "usage: %s replies|replies-bf16|replies-fp8|replies-f16|replies-rest|parse\n", argv[0]);
   return 2;
 }
