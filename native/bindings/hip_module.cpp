@@ -48,7 +48,7 @@ py::dict to_dict(const mi355x_probe_result& r) {
 }  // namespace
 
 // mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result / _f16_result / _f64_result /
-// _f6f4_result / _sparse_result / _gemm_result / _splitk_result / _attn_result (the same
+// _f6f4_result / _sparse_result / _gemm_result / _splitk_result / _attn_result / _mxgemm_result (the same
 // fields; stage_bad differs in length)
 template <typename R>
 py::dict datapath_dict(const R& r) {
@@ -85,7 +85,7 @@ py::dict datapath_dict(const R& r) {
   return d;
 }
 
-// what the GEMM, split-K and attention results carry beyond datapath_dict
+// what the GEMM, split-K, attention and MXFP4 GEMM results carry beyond datapath_dict
 template <typename R>
 void add_extras(py::dict&, const R&) {}
 void add_extras(py::dict& d, const mi355x_datapath_gemm_result& r) {
@@ -100,6 +100,11 @@ void add_extras(py::dict& d, const mi355x_datapath_splitk_result& r) {
   d["xccs_per_tile_min"] = r.xccs_per_tile_min;
   d["fill_us"] = r.fill_us;
   d["drain_us"] = r.drain_us;
+  d["verify_us"] = r.verify_us;
+}
+void add_extras(py::dict& d, const mi355x_datapath_mxgemm_result& r) {
+  d["ksteps"] = r.ksteps;
+  d["fill_us"] = r.fill_us;
   d["verify_us"] = r.verify_us;
 }
 void add_extras(py::dict& d, const mi355x_datapath_attn_result& r) {
@@ -220,4 +225,5 @@ PYBIND11_MODULE(_hip, m) {
   def_datapath_check(m, "hsa_datapath_gemm_check", mi355x_hsa_datapath_gemm_check);
   def_datapath_check(m, "hsa_datapath_splitk_check", mi355x_hsa_datapath_splitk_check);
   def_datapath_check(m, "hsa_datapath_attn_check", mi355x_hsa_datapath_attn_check);
+  def_datapath_check(m, "hsa_datapath_mxgemm_check", mi355x_hsa_datapath_mxgemm_check);
 }

@@ -708,6 +708,60 @@ int mi355x_hsa_datapath_attn_check(int ordinal, uint32_t nonce, double timeout_s
 // (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
 void mi355x_hsa_datapath_attn_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- MXFP4 GEMM pipeline check (scaled-MFMA chains from HBM, bit-exact) ----
+// The GEMM checks above are bf16. Here (datapath_mxgemm_kernel.h) mi355x_mxgemm_fill
+// writes a packed e2m1 A panel and its E8M0 block scales per workgroup, and one
+// shared K-major B panel with its scales, into device memory;
+// mi355x_mfma_datapath_mxgemm, one workgroup per CU, moves the operands into LDS
+// with global_load_lds_dwordx4 and out of it with ds_read_b128 (one read is one
+// lane's 32-element fragment, one scale block), loads the scale bytes into
+// registers a step ahead, gathers them with v_perm_b32, and runs dependent chains
+// of 4 * ksteps v_mfma_scale_f32_32x32x64_f8f6f4 per accumulator, each with its
+// own op_sel byte of the scale VGPRs. Every D word is exact in any order, so the
+// host checks every one (datapath_mxgemm_verify.h) and, per wave, a fold of the
+// fragments and of the scale VGPRs. stage_bad: wrong fold words of the A feed,
+// of the B feed, of the scale feed, wrong D words; mfma_bad = the three feeds'
+// sum, tile_bad = the D words; records_ok counts exact workgroups.
+// first_bad_word: wg * 16 + wave * 2 + {xor, sum} for stages 0, 1 and 2,
+// wg * 16384 + row * 128 + column for stage 3.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int ksteps;             // K / 256
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[4];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double fill_us;         // GPU time of mi355x_mxgemm_fill
+  double kernel_us;       // GPU time of mi355x_mfma_datapath_mxgemm
+  double verify_us;       // host time of the verdict
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_mxgemm_result;
+
+int mi355x_hsa_datapath_mxgemm_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_mxgemm_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later MXFP4 GEMM check: bit `bit` of word `word`
+// (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
+void mi355x_hsa_datapath_mxgemm_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,3 +13,4 @@
 #include "datapath_gemm_kernel.hip"
 #include "datapath_splitk_kernel.hip"
 #include "datapath_attn_kernel.hip"
+#include "datapath_mxgemm_kernel.hip"

@@ -11,7 +11,8 @@
 // mi355x_hsa_datapath_sparse_check: the 2:4 sparse forms, v_smfmac_*;
 // mi355x_hsa_datapath_gemm_check: a bf16 GEMM out of HBM through LDS;
 // mi355x_hsa_datapath_splitk_check: split-K partials summed by L2 atomics;
-// mi355x_hsa_datapath_attn_check: a flash-attention loop, MFMA to softmax to MFMA), all on the
+// mi355x_hsa_datapath_attn_check: a flash-attention loop, MFMA to softmax to MFMA;
+// mi355x_hsa_datapath_mxgemm_check: an MXFP4 GEMM, scaled-MFMA chains out of HBM), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -42,6 +43,7 @@
 #include "datapath_sparse_verify.h"
 #include "datapath_splitk_verify.h"
 #include "datapath_attn_verify.h"
+#include "datapath_mxgemm_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_json.h"
@@ -840,6 +842,70 @@ extern "C" int mi355x_hsa_datapath_attn_check(int ordinal, uint32_t nonce, doubl
   }
   const auto t_verify = std::chrono::steady_clock::now();
   mi355x::datapath_attn_verdict(records, ml, o, heads, MI355X_DPAT_QBLOCKS, MI355X_DPAT_KBLOCKS, out);
+  out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_mxgemm_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_mxgemm", stage, word, bit, ordinal);
+}
+
+extern "C" int mi355x_hsa_datapath_mxgemm_check(int ordinal, uint32_t nonce, double timeout_s,
+                                                mi355x_datapath_mxgemm_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_mxgemm_result>(ordinal, nonce);
+  out->ksteps = MI355X_DPMX_KSTEPS;
+  Check<mi355x_datapath_mxgemm_result> c(ordinal, timeout_s, out);
+  KernelInfo ks[2];  // fill, gemm
+  // the operands and scales live in device memory; records, D tiles and kernargs in host pools
+  if (!c.begin(true, &mi355x_datapath_mxgemm_result::grid, 1, "datapath_mxgemm",
+               {{"mi355x_mxgemm_fill.kd", sizeof(mi355x_datapath_mxgemm_args)},
+                {"mi355x_mfma_datapath_mxgemm.kd", sizeof(mi355x_datapath_mxgemm_args)}},
+               ks))
+    return 1;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
+  if (!dpmx_sizes_ok(grid, MI355X_DPMX_KSTEPS)) {
+    std::snprintf(out->error, sizeof(out->error), "datapath mxgemm check: %u workgroups", grid);
+    return c.finish();
+  }
+  const size_t K = static_cast<size_t>(MI355X_DPMX_KSTEPS) * MI355X_DPMX_KSTEP;
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPMX_REC_WORDS * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPMX_WG_WORDS * sizeof(uint32_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  // written by mi355x_mxgemm_fill, whole, before the GEMM reads them: no runtime fill or copy (ROCr would open a queue)
+  auto* a = c.bufs.alloc<uint8_t>(c.ag->coarse, grid * MI355X_DPMX_TILE * K / 2, "alloc A");
+  auto* b = c.bufs.alloc<uint8_t>(c.ag->coarse, MI355X_DPMX_TILE * K / 2, "alloc B");
+  auto* sa = c.bufs.alloc<uint8_t>(c.ag->coarse, grid * MI355X_DPMX_TILE * K / 32, "alloc A scales");
+  auto* sb = c.bufs.alloc<uint8_t>(c.ag->coarse, MI355X_DPMX_TILE * K / 32, "alloc B scales");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_mxgemm_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->a = a;
+  kargs->b = b;
+  kargs->sa = sa;
+  kargs->sb = sb;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  kargs->ksteps = MI355X_DPMX_KSTEPS;
+  if (!c.run(ks[0], kargs, grid, MI355X_DPMX_THREADS, "datapath mxgemm fill", &out->fill_us) ||
+      !c.run(ks[1], kargs, grid, MI355X_DPMX_THREADS, "datapath mxgemm check", &out->kernel_us))
+    return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = dp_corrupt("datapath_mxgemm");
+    const int words = static_cast<int>(cr[0] == 3 ? grid * MI355X_DPMX_WG_WORDS : grid * 16);
+    if (cr[0] >= 0 && cr[0] < MI355X_DPMX_STAGES && cr[1] >= 0 && cr[1] < words && (cr[0] == 3 || cr[1] % 16 < 8) &&
+        cr[2] >= 0 && cr[2] < 32 && (cr[3] < 0 || cr[3] == ordinal))
+      (cr[0] == 3 ? tiles[cr[1]]
+                  : records[(cr[1] / 16) * MI355X_DPMX_REC_WORDS + dpmx_fold_slot(cr[0], cr[1] % 16)]) ^= 1u << cr[2];
+  }
+  const auto t_verify = std::chrono::steady_clock::now();
+  mi355x::datapath_mxgemm_verdict(records, tiles, grid, MI355X_DPMX_KSTEPS, out);
   out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
 }

@@ -32,6 +32,7 @@ inline constexpr ProbeKind kProbeKinds[] = {
     {"datapath_gemm", "-gemm"},
     {"datapath_splitk", "-splitk"},
     {"datapath_attn", "-attn"},
+    {"datapath_mxgemm", "-mxgemm"},
 };
 inline constexpr int kProbeKindCount = static_cast<int>(sizeof(kProbeKinds) / sizeof(kProbeKinds[0]));
 

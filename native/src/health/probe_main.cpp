@@ -16,6 +16,7 @@
 //   mi355x-liveness-probe --datapath-gemm [--devices ..] (a bf16 GEMM out of HBM through LDS, see mi355x_mfma_datapath_gemm)
 //   mi355x-liveness-probe --datapath-splitk [--devices ..] (split-K partials summed by L2 atomics, see mi355x_mfma_datapath_splitk)
 //   mi355x-liveness-probe --datapath-attn [--devices ..] (a flash-attention loop, see mi355x_mfma_datapath_attn)
+//   mi355x-liveness-probe --datapath-mxgemm [--devices ..] (an MXFP4 GEMM out of HBM, see mi355x_mfma_datapath_mxgemm)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
@@ -32,6 +33,8 @@
 //       3 = ledger word; W numbered over all tiles, as first_bad_word)
 //   --corrupt-datapath-attn S:W:B[@O]: the same for the attention check (S 0 = K fold, 1 = V fold, 2 = m / l word,
 //       3 = O word; W numbered over all workgroups, as first_bad_word)
+//   --corrupt-datapath-mxgemm S:W:B[@O]: the same for the MXFP4 GEMM check (S 0 = A fold, 1 = B fold, 2 = scale fold,
+//       3 = D word; W numbered over all workgroups, as first_bad_word)
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -350,7 +353,7 @@ constexpr DatapathOps kDatapathOps[] = {
     MI355X_DATAPATH_OPS(datapath),        MI355X_DATAPATH_OPS(datapath_i8),     MI355X_DATAPATH_OPS(datapath_bf16),
     MI355X_DATAPATH_OPS(datapath_fp8),    MI355X_DATAPATH_OPS(datapath_f16),    MI355X_DATAPATH_OPS(datapath_f64),
     MI355X_DATAPATH_OPS(datapath_f6f4),   MI355X_DATAPATH_OPS(datapath_sparse), MI355X_DATAPATH_OPS(datapath_gemm),
-    MI355X_DATAPATH_OPS(datapath_splitk), MI355X_DATAPATH_OPS(datapath_attn),
+    MI355X_DATAPATH_OPS(datapath_splitk), MI355X_DATAPATH_OPS(datapath_attn),   MI355X_DATAPATH_OPS(datapath_mxgemm),
 };
 #undef MI355X_DATAPATH_OPS
 // kDatapathOps[i] belongs to kProbeKinds[i]

@@ -181,6 +181,31 @@ def datapath_gemm_verdict(cli, image: bytes, grid: int, nonce: int, ksteps: int,
                           text=True, timeout=120)
 
 
+def datapath_mxgemm_cli(build_dir: Path) -> Path:
+    """native/tests/datapath_mxgemm_contract_cli.cpp, found or compiled like contract_cli()."""
+    from .. import _build
+    exe = _build.DATAPATH_MXGEMM_CLI
+    if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
+        return exe
+    return compile_cli(Path(build_dir) / "datapath_mxgemm_contract_cli",
+                       source=REPO / "native" / "tests" / "datapath_mxgemm_contract_cli.cpp")
+
+
+def datapath_mxgemm_image(cli, grid: int, nonce: int, ksteps: int, command: str = "image") -> bytes:
+    """`datapath_mxgemm_contract_cli image` (or `operands`): the header's records and D tiles (operands and scales)."""
+    return subprocess.run([str(cli), command, str(grid), str(nonce), str(ksteps)], capture_output=True, check=True,
+                          timeout=120).stdout
+
+
+def datapath_mxgemm_verdict(cli, image: bytes, grid: int, nonce: int, ksteps: int, work) -> subprocess.CompletedProcess:
+    """`datapath_mxgemm_contract_cli verdict` on `image`, written into the directory `work`: stdout is one
+    datapath_mxgemm_json line; exit 2 and no line for an image of another length."""
+    path = Path(work) / "datapath_mxgemm_image.bin"
+    path.write_bytes(image)
+    return subprocess.run([str(cli), "verdict", str(grid), str(nonce), str(ksteps), str(path)], capture_output=True,
+                          text=True, timeout=120)
+
+
 def datapath_splitk_cli(build_dir: Path) -> Path:
     """native/tests/datapath_splitk_contract_cli.cpp, found or compiled like contract_cli()."""
     from .. import _build

@@ -35,6 +35,12 @@ REQUESTS.json is a list of requests, run in order:
         with the inject build "inject" is {"kind": "s" or "o", "wg": w, "wave": v, "lane": l, "index": accumulator word,
         "mask": m})
 
+    {"id": ..., "kernel": "datapath_mxgemm", "nonce": n, "grid": g, "ksteps": k[, "launch_grid": ...]}
+        (mi355x_mxgemm_fill, then mi355x_mfma_datapath_mxgemm, on the same arguments; with the inject build "inject" is
+        {"kind": "mfma", "wg", "wave", "lane", "index", "mask"}, {"kind": "lds", "wg", "step", "index", "mask"},
+        {"kind": "hbm", "wg", "index": byte of A, "mask"} or {"kind": "scale", "wg", "wave", "lane",
+        "index": step * 16 + sub-step * 4 + scale VGPR, "mask"})
+
 A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64, datapath_f6f4 or datapath_sparse request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
 the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h /
@@ -269,6 +275,21 @@ class DatapathAttnInjectArgs(ctypes.Structure):
 DATAPATH_ATTN_ARG_STRUCTS = {"mi355x_datapath_attn_args": DatapathAttnArgs}
 DATAPATH_ATTN_INJECT_ARG_STRUCTS = {"mi355x_datapath_attn_args": DatapathAttnInjectArgs}
 DATAPATH_ATTN_INJECT_KINDS = {"none": 0, "s": 1, "o": 2}   # MI355X_DPAT_INJECT_*
+
+
+class DatapathMxgemmArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("a", _ptr), ("b", _ptr), ("sa", _ptr), ("sb", _ptr),
+                ("nonce", _u32), ("grid", _u32), ("ksteps", _u32), ("pad", _u32)]
+
+
+class DatapathMxgemmInjectArgs(ctypes.Structure):
+    _fields_ = DatapathMxgemmArgs._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_mxgemm_kernel.h; both kernels of the check take the one struct
+DATAPATH_MXGEMM_ARG_STRUCTS = {"mi355x_datapath_mxgemm_args": DatapathMxgemmArgs}
+DATAPATH_MXGEMM_INJECT_ARG_STRUCTS = {"mi355x_datapath_mxgemm_args": DatapathMxgemmInjectArgs}
+DATAPATH_MXGEMM_INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2, "hbm": 3, "scale": 4}   # MI355X_DPMX_INJECT_*
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -280,6 +301,9 @@ def inject_words(req: dict) -> tuple:
         return (INJECT_KINDS["none"], 0, 0, 0, 0, 0)
     if req["kernel"] == "datapath_gemm":                 # the wave field carries the step of an lds injection
         return (DATAPATH_GEMM_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj.get("wave", inj.get("step", 0))),
+                int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
+    if req["kernel"] == "datapath_mxgemm":               # likewise
+        return (DATAPATH_MXGEMM_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj.get("wave", inj.get("step", 0))),
                 int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
     if req["kernel"] == "datapath_splitk":
         return (DATAPATH_SPLITK_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj["wave"]), int(inj["lane"]),
@@ -302,7 +326,7 @@ def code_object_of(req: dict) -> str:
     if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                                                    "datapath_f16", "datapath_f64", "datapath_f6f4",
                                                    "datapath_sparse", "datapath_gemm", "datapath_splitk",
-                                                   "datapath_attn"):
+                                                   "datapath_attn", "datapath_mxgemm"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -322,10 +346,11 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "datapath_sparse": ("mi355x_mfma_datapath_sparse", 256),
            "datapath_gemm": ("mi355x_mfma_datapath_gemm", 256),
            "datapath_splitk": ("mi355x_mfma_datapath_splitk", 256),
-           "datapath_attn": ("mi355x_mfma_datapath_attn", 256)}
+           "datapath_attn": ("mi355x_mfma_datapath_attn", 256),
+           "datapath_mxgemm": ("mi355x_mfma_datapath_mxgemm", 256)}
 # kernel -> (symbol, lanes) of a kernel launched before it (FIRST) or after it (LAST), on the same arguments and workgroups
 FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256), "datapath_splitk": ("mi355x_splitk_fill", 256),
-         "datapath_attn": ("mi355x_attn_fill", 256)}
+         "datapath_attn": ("mi355x_attn_fill", 256), "datapath_mxgemm": ("mi355x_mxgemm_fill", 256)}
 LAST = {"datapath_splitk": ("mi355x_splitk_drain", 256)}
 
 _H2D, _D2H = 1, 2
@@ -572,6 +597,23 @@ def plan(req: dict, base_dir: Path):
             raise ValueError("launch_grid below heads * qblocks")
         cls, tail = (DatapathAttnInjectArgs, inject_words(req)) if inject else (DatapathAttnArgs, ())
         return bufs, lambda p: cls(p["records"], p["ml"], p["tiles"], p["q"], p["k"], p["v"], req["nonce"], h, qb, kb,
+                                   *tail), wgs
+    if k == "datapath_mxgemm":
+        g, ksteps = int(req["grid"]), int(req["ksteps"])
+        if not 1 <= g <= 1024 or not 1 <= ksteps <= 8:
+            raise ValueError("grid outside 1..1024 or ksteps outside 1..8")   # the buffers are sized by them
+        bufs = [("records", np.uint32, _filled(g * 32 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * 128 * 128 * 4, OUT_PREFILL)),
+                ("a", np.uint8, _filled(g * 128 * ksteps * 128, OUT_PREFILL)),
+                ("b", np.uint8, _filled(128 * ksteps * 128, OUT_PREFILL)),
+                ("sa", np.uint8, _filled(g * 128 * ksteps * 8, OUT_PREFILL)),
+                ("sb", np.uint8, _filled(128 * ksteps * 8, OUT_PREFILL))]
+        inject = code_object_of(req) == "inject"
+        wgs = g if inject else int(req.get("launch_grid", g))
+        if wgs < g:
+            raise ValueError("launch_grid below grid")
+        cls, tail = (DatapathMxgemmInjectArgs, inject_words(req)) if inject else (DatapathMxgemmArgs, ())
+        return bufs, lambda p: cls(p["records"], p["tiles"], p["a"], p["b"], p["sa"], p["sb"], req["nonce"], g, ksteps, 0,
                                    *tail), wgs
     raise ValueError(f"unknown kernel {k!r}")
 

@@ -49,6 +49,8 @@ bf16 GEMM pipeline-check replies ("datapath_gemm" requests /
 --datapath-gemm) follow the "datapath_gemm" map and append "datapath_gemm:<host ordinal>".
 Split-K GEMM check replies ("datapath_splitk" requests /
 --datapath-splitk) follow the "datapath_splitk" map and append "datapath_splitk:<host ordinal>".
+MXFP4 GEMM pipeline-check replies ("datapath_mxgemm" requests /
+--datapath-mxgemm) follow the "datapath_mxgemm" map and append "datapath_mxgemm:<host ordinal>".
 Fused attention check replies ("datapath_attn" requests /
 --datapath-attn) follow the "datapath_attn" map and append "datapath_attn:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
@@ -106,7 +108,8 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
 
 
 DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16", "datapath_f64",
-                  "datapath_f6f4", "datapath_sparse", "datapath_gemm", "datapath_splitk", "datapath_attn")
+                  "datapath_f6f4", "datapath_sparse", "datapath_gemm", "datapath_splitk", "datapath_attn",
+                  "datapath_mxgemm")
 
 
 def _log_check(kind, host_ordinal):
@@ -391,6 +394,35 @@ def _datapath_attn_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return d
 
 
+# the shipped verdict's figures for the mxgemm kind's faults at nonce 0x5EED142F (testing/probe_contract.py builds them):
+# stuck_bit = bit 30 of the 128 D words of row 0 of workgroup 17 (its first word's healthy value), device_bad = fold
+# word 1 of the A feed of workgroup 17 off by 12 (its healthy value)
+STUCK_MXGEMM = (128, 17 * 16384, 1219074640)
+FEED_MXGEMM = (17 * 16 + 1, 1055928994)
+
+
+def _datapath_mxgemm_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """MXFP4 GEMM pipeline-check reply (kind "datapath_mxgemm"; stages: A feed, B feed, scale feed, D words); the modes
+    of _datapath_device, from the control file's "datapath_mxgemm" map."""
+    stuck = dict(records_ok=255, tile_bad=STUCK_MXGEMM[0], stage_bad=[0, 0, 0, STUCK_MXGEMM[0]], first_bad_wg=17,
+                 first_bad_stage=3, first_bad_word=STUCK_MXGEMM[1], first_bad_got=STUCK_MXGEMM[2] ^ 0x40000000,
+                 first_bad_want=STUCK_MXGEMM[2], first_bad_xor=0x40000000,
+                 error=f"255/256 workgroups exact (feed_bad=0 scale_bad=0 d_bad={STUCK_MXGEMM[0]}); first bad: wg 17 "
+                       f"stage 3 word {STUCK_MXGEMM[1]} xor 0x40000000 (bit 30)")
+    d = _datapath_reply(ordinal_reported, "ok" if mode == "device_bad" else mode, nonce, host_ordinal, 4, stuck, 120.0,
+                        60000.0, kind="datapath_mxgemm")
+    d.update(ksteps=8, fill_us=40.0, verify_us=50000.0)
+    if mode == "missing":
+        d.update(error="254/256 workgroups exact (feed_bad=0 scale_bad=0 d_bad=0)")
+    elif mode == "device_bad":
+        d.update(ok=False, records_ok=255, mfma_bad=1, stage_bad=[1, 0, 0, 0], first_bad_wg=17, first_bad_stage=0,
+                 first_bad_word=FEED_MXGEMM[0], first_bad_got=FEED_MXGEMM[1] + 12, first_bad_want=FEED_MXGEMM[1],
+                 first_bad_xor=12,
+                 error=f"255/256 workgroups exact (feed_bad=1 scale_bad=0 d_bad=0); first bad: wg 17 stage 0 word "
+                       f"{FEED_MXGEMM[0]} xor 0x0000000c")
+    return d
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
                 "datapath_fp8": _datapath_fp8_device,
@@ -400,7 +432,8 @@ CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datap
                 "datapath_sparse": _datapath_sparse_device,
                 "datapath_gemm": _datapath_gemm_device,
                 "datapath_splitk": _datapath_splitk_device,
-                "datapath_attn": _datapath_attn_device}
+                "datapath_attn": _datapath_attn_device,
+                "datapath_mxgemm": _datapath_mxgemm_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -479,6 +512,7 @@ _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapa
           ("datapath_gemm", (_FLOAT,)),
           ("datapath_splitk", (_FLOAT,)),
           ("datapath_attn", (_FLOAT,)),
+          ("datapath_mxgemm", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -776,6 +810,7 @@ def main(argv):
                        ("--datapath-gemm", "datapath_gemm"),
                        ("--datapath-splitk", "datapath_splitk"),
                        ("--datapath-attn", "datapath_attn"),
+                       ("--datapath-mxgemm", "datapath_mxgemm"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
