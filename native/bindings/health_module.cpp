@@ -66,6 +66,7 @@ class PyHealthEngine {
     i("datapath_splitk_check_every", &c.datapath_splitk_check_every);
     i("datapath_attn_check_every", &c.datapath_attn_check_every);
     i("datapath_mxgemm_check_every", &c.datapath_mxgemm_check_every);
+    i("datapath_mxquant_check_every", &c.datapath_mxquant_check_every);
     d("perf_min_hbm_read_gbps", &c.perf_min_hbm_read_gbps);
     d("perf_min_hbm_write_gbps", &c.perf_min_hbm_write_gbps);
     d("perf_min_mfma_tflops", &c.perf_min_mfma_tflops);
@@ -142,6 +143,8 @@ class PyHealthEngine {
     d["datapath_attn_failures"] = eng_->datapath_attn_failures();
     d["datapath_mxgemm_checks"] = eng_->datapath_mxgemm_checks();
     d["datapath_mxgemm_failures"] = eng_->datapath_mxgemm_failures();
+    d["datapath_mxquant_checks"] = eng_->datapath_mxquant_checks();
+    d["datapath_mxquant_failures"] = eng_->datapath_mxquant_failures();
     if (auto* p = eng_->prober()) {
       d["server_starts"] = p->server_starts.load();
       d["server_restarts"] = p->server_restarts.load();

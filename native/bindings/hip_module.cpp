@@ -48,7 +48,7 @@ py::dict to_dict(const mi355x_probe_result& r) {
 }  // namespace
 
 // mi355x_datapath_result or mi355x_datapath_i8_result / _bf16_result / _fp8_result / _f16_result / _f64_result /
-// _f6f4_result / _sparse_result / _gemm_result / _splitk_result / _attn_result / _mxgemm_result (the same
+// _f6f4_result / _sparse_result / _gemm_result / _splitk_result / _attn_result / _mxgemm_result / _mxquant_result (the same
 // fields; stage_bad differs in length)
 template <typename R>
 py::dict datapath_dict(const R& r) {
@@ -85,7 +85,7 @@ py::dict datapath_dict(const R& r) {
   return d;
 }
 
-// what the GEMM, split-K, attention and MXFP4 GEMM results carry beyond datapath_dict
+// what the GEMM, split-K, attention, MXFP4 GEMM and MX quantise results carry beyond datapath_dict
 template <typename R>
 void add_extras(py::dict&, const R&) {}
 void add_extras(py::dict& d, const mi355x_datapath_gemm_result& r) {
@@ -104,6 +104,11 @@ void add_extras(py::dict& d, const mi355x_datapath_splitk_result& r) {
 }
 void add_extras(py::dict& d, const mi355x_datapath_mxgemm_result& r) {
   d["ksteps"] = r.ksteps;
+  d["fill_us"] = r.fill_us;
+  d["verify_us"] = r.verify_us;
+}
+void add_extras(py::dict& d, const mi355x_datapath_mxquant_result& r) {
+  d["hsteps"] = r.hsteps;
   d["fill_us"] = r.fill_us;
   d["verify_us"] = r.verify_us;
 }
@@ -226,4 +231,5 @@ PYBIND11_MODULE(_hip, m) {
   def_datapath_check(m, "hsa_datapath_splitk_check", mi355x_hsa_datapath_splitk_check);
   def_datapath_check(m, "hsa_datapath_attn_check", mi355x_hsa_datapath_attn_check);
   def_datapath_check(m, "hsa_datapath_mxgemm_check", mi355x_hsa_datapath_mxgemm_check);
+  def_datapath_check(m, "hsa_datapath_mxquant_check", mi355x_hsa_datapath_mxquant_check);
 }

@@ -225,6 +225,8 @@ struct Config {
   int datapath_attn_check_every = 0;
   // and for the MXFP4 GEMM pipeline check (scaled-MFMA chains from HBM), likewise (0 = off)
   int datapath_mxgemm_check_every = 0;
+  // and for the MX quantise check (MFMA, scaled convert, scaled MFMA), likewise (0 = off)
+  int datapath_mxquant_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_hbm_write_gbps = 2000.0;
   double perf_min_mfma_tflops = 700.0;
@@ -331,6 +333,10 @@ class Engine {
   uint64_t datapath_mxgemm_failures() const { return datapath_mxgemm_.failures; }
   // and for the MXFP4 GEMM pipeline check
   std::map<std::string, std::string> datapath_mxgemm_failed() const;
+  uint64_t datapath_mxquant_checks() const { return datapath_mxquant_.checks; }
+  uint64_t datapath_mxquant_failures() const { return datapath_mxquant_.failures; }
+  // and for the MX quantise check
+  std::map<std::string, std::string> datapath_mxquant_failed() const;
   // device -> (ok | degraded | failed, reason) of its last throughput check
   std::map<std::string, std::pair<std::string, std::string>> perf_verdicts() const;
   std::map<std::string, ProbeOutcome> perf_last() const;  // device -> its last throughput-check reply
@@ -383,9 +389,9 @@ class Engine {
     uint64_t checks = 0, failures = 0;
     std::map<std::string, std::string> failed;  // guarded by mu_
   };
-  struct DatapathKind;  // the f32, int8, bf16, fp8, f16, f64, f6f4, sparse, gemm, splitk, attn or mxgemm check: request verb, wording, series names
+  struct DatapathKind;  // the f32, int8, bf16, fp8, f16, f64, f6f4, sparse, gemm, splitk, attn, mxgemm or mxquant check: request verb, wording, series names
   static const DatapathKind kDatapathF32, kDatapathI8, kDatapathBf16, kDatapathFp8, kDatapathF16, kDatapathF64,
-      kDatapathF6F4, kDatapathSparse, kDatapathGemm, kDatapathSplitk, kDatapathAttn, kDatapathMxgemm;
+      kDatapathF6F4, kDatapathSparse, kDatapathGemm, kDatapathSplitk, kDatapathAttn, kDatapathMxgemm, kDatapathMxquant;
   void datapath_check(const std::map<std::string, int>& ords, const DatapathKind& kind, DatapathState* st);
   SmiXgmiSnapshot read_xgmi();
 
@@ -409,7 +415,7 @@ class Engine {
   std::map<std::string, ProbeOutcome> perf_last_;                     // guarded by mu_
   // each check keeps failures of its own
   DatapathState datapath_, datapath_i8_, datapath_bf16_, datapath_fp8_, datapath_f16_, datapath_f64_,
-      datapath_f6f4_, datapath_sparse_, datapath_gemm_, datapath_splitk_, datapath_attn_, datapath_mxgemm_;
+      datapath_f6f4_, datapath_sparse_, datapath_gemm_, datapath_splitk_, datapath_attn_, datapath_mxgemm_, datapath_mxquant_;
   uint64_t xgmi_readings_ = 0;
   double last_sweep_ms_ = 0;
   int abort_fd_ = -1;

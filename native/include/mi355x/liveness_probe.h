@@ -762,6 +762,61 @@ int mi355x_hsa_datapath_mxgemm_check(int ordinal, uint32_t nonce, double timeout
 // (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
 void mi355x_hsa_datapath_mxgemm_corrupt(int stage, int word, int bit, int ordinal);
 
+// ---- MX quantise check (MFMA, scaled convert, scaled MFMA, bit-exact) ----
+// The checks above take their e2m1 operands and E8M0 scales ready-made. Here
+// (datapath_mxquant_kernel.h) mi355x_mxquant_fill writes a bf16 token panel X per
+// workgroup and shared W1 (bf16), W2 (packed e2m1, K-major) and W2's scale bytes;
+// mi355x_mfma_datapath_mxquant, one workgroup per CU, runs a two-layer MLP tile:
+// per slab of 128 hidden columns H^T = W1 . X^T by v_mfma_f32_32x32x16_bf16, the
+// absolute maximum of each 32-wide block (v_max3_f32, v_permlane32_swap), the
+// E8M0 byte from its exponent field, v_cvt_scalef32_pk_fp4_f32 to packed e2m1,
+// an LDS round trip, and Y += Q . W2^T by v_mfma_scale_f32_32x32x64_f8f6f4 with
+// the block scales just made. Every code, scale byte and Y word is exact, so the
+// host checks every one (datapath_mxquant_verify.h). stage_bad: wrong fold words
+// of the W1 feed, of the W2 and scale feed, wrong dwords of the quantised image,
+// wrong Y words; mfma_bad = the two feeds' sum, tile_bad = the Y words;
+// records_ok counts exact workgroups. first_bad_word: wg * 16 + wave * 2 +
+// {xor, sum} for stage 0, wg * 16 + wave * 4 + {W2 xor, W2 sum, scale xor, scale
+// sum} for stage 1, wg * 2176 * hsteps + dword for stage 2, wg * 16384 + row *
+// 128 + column for stage 3.
+typedef struct {
+  int ordinal;
+  int ok;
+  int hsa_error;
+  uint32_t nonce;
+  int grid;
+  int hsteps;             // hidden / 128
+  int cu_count;
+  int num_xcc;
+  int records_ok;
+  uint32_t mfma_bad;
+  uint32_t stage_bad[4];
+  uint32_t tile_bad;
+  int first_bad_wg;
+  int first_bad_stage;
+  int first_bad_word;
+  uint32_t first_bad_got;
+  uint32_t first_bad_want;
+  uint32_t first_bad_xor;
+  int cus_covered;
+  int simds_covered;
+  int xccs_covered;
+  double fill_us;         // GPU time of mi355x_mxquant_fill
+  double kernel_us;       // GPU time of mi355x_mfma_datapath_mxquant
+  double verify_us;       // host time of the verdict
+  double total_us;
+  double in_flight_s;
+  int kept_queue;
+  int kfd_node_id;
+  char pci_bus_id[32];
+  char error[160];
+} mi355x_datapath_mxquant_result;
+
+int mi355x_hsa_datapath_mxquant_check(int ordinal, uint32_t nonce, double timeout_s, mi355x_datapath_mxquant_result* out);
+// Debug fault injection, as mi355x_hsa_datapath_i8_corrupt, for every later MX quantise check: bit `bit` of word `word`
+// (numbered as first_bad_word) of the stage-`stage` data is flipped before the verdict.
+void mi355x_hsa_datapath_mxquant_corrupt(int stage, int word, int bit, int ordinal);
+
 #ifdef __cplusplus
 }
 #endif

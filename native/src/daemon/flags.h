@@ -70,6 +70,7 @@ struct Flags {
   int datapath_splitk_check_every = 0;
   int datapath_attn_check_every = 0;
   int datapath_mxgemm_check_every = 0;
+  int datapath_mxquant_check_every = 0;
   double perf_min_hbm_read_gbps = 3000.0;
   double perf_min_mfma_tflops = 700.0;
   double perf_min_xcd_clock_ratio = 0.6;

@@ -57,6 +57,7 @@ health::Config engine_config(const Flags& f) {
   hc.datapath_splitk_check_every = f.datapath_splitk_check_every;
   hc.datapath_attn_check_every = f.datapath_attn_check_every;
   hc.datapath_mxgemm_check_every = f.datapath_mxgemm_check_every;
+  hc.datapath_mxquant_check_every = f.datapath_mxquant_check_every;
   hc.perf_min_hbm_read_gbps = f.perf_min_hbm_read_gbps;
   hc.perf_min_mfma_tflops = f.perf_min_mfma_tflops;
   hc.perf_min_xcd_clock_ratio = f.perf_min_xcd_clock_ratio;

@@ -550,6 +550,10 @@ const Engine::DatapathKind Engine::kDatapathMxgemm = {
     "datapath_mxgemm", "datapath mxgemm check", "health.datapath_mxgemm_check", "mi355x_dp_datapath_mxgemm_checks_total",
     "MXFP4 GEMM pipeline checks run (scaled-MFMA chains from HBM, bit-exact, on the idle GPUs)",
     "mi355x_dp_datapath_mxgemm_check_failures_total", "MXFP4 GEMM pipeline checks that did not pass"};
+const Engine::DatapathKind Engine::kDatapathMxquant = {
+    "datapath_mxquant", "datapath mxquant check", "health.datapath_mxquant_check", "mi355x_dp_datapath_mxquant_checks_total",
+    "MX quantise checks run (MFMA, scaled convert, scaled MFMA, bit-exact, on the idle GPUs)",
+    "mi355x_dp_datapath_mxquant_check_failures_total", "MX quantise checks that did not pass"};
 
 void Engine::liveness_pass(Reasons* reasons) {
   std::map<std::string, int> ords = judged_ordinals(*reasons);
@@ -598,7 +602,8 @@ void Engine::liveness_pass(Reasons* reasons) {
       {cfg_.datapath_gemm_check_every, {&kDatapathGemm, &datapath_gemm_}},
       {cfg_.datapath_splitk_check_every, {&kDatapathSplitk, &datapath_splitk_}},
       {cfg_.datapath_attn_check_every, {&kDatapathAttn, &datapath_attn_}},
-      {cfg_.datapath_mxgemm_check_every, {&kDatapathMxgemm, &datapath_mxgemm_}}};
+      {cfg_.datapath_mxgemm_check_every, {&kDatapathMxgemm, &datapath_mxgemm_}},
+      {cfg_.datapath_mxquant_check_every, {&kDatapathMxquant, &datapath_mxquant_}}};
   for (const auto& [every, check] : datapath_checks) {
     if (every <= 0 || sweeps_ % static_cast<uint64_t>(every) != 0) continue;
     std::map<std::string, int> cand;
@@ -610,7 +615,7 @@ void Engine::liveness_pass(Reasons* reasons) {
   for (const DatapathState* st :
        {&datapath_, &datapath_i8_, &datapath_bf16_, &datapath_fp8_, &datapath_f16_, &datapath_f64_,
         &datapath_f6f4_, &datapath_sparse_, &datapath_gemm_, &datapath_splitk_, &datapath_attn_,
-        &datapath_mxgemm_})
+        &datapath_mxgemm_, &datapath_mxquant_})
     for (const auto& [id, why] : st->failed)
       if (reasons->count(id)) (*reasons)[id].push_back(why);
   for (const auto& [id, pv] : perf_)
@@ -1172,6 +1177,11 @@ std::map<std::string, std::string> Engine::datapath_attn_failed() const {
 std::map<std::string, std::string> Engine::datapath_mxgemm_failed() const {
   std::lock_guard<std::mutex> lk(mu_);
   return datapath_mxgemm_.failed;
+}
+
+std::map<std::string, std::string> Engine::datapath_mxquant_failed() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return datapath_mxquant_.failed;
 }
 
 std::map<std::string, ProbeOutcome> Engine::perf_last() const {

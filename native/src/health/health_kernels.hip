@@ -14,3 +14,4 @@
 #include "datapath_splitk_kernel.hip"
 #include "datapath_attn_kernel.hip"
 #include "datapath_mxgemm_kernel.hip"
+#include "datapath_mxquant_kernel.hip"

@@ -12,7 +12,8 @@
 // mi355x_hsa_datapath_gemm_check: a bf16 GEMM out of HBM through LDS;
 // mi355x_hsa_datapath_splitk_check: split-K partials summed by L2 atomics;
 // mi355x_hsa_datapath_attn_check: a flash-attention loop, MFMA to softmax to MFMA;
-// mi355x_hsa_datapath_mxgemm_check: an MXFP4 GEMM, scaled-MFMA chains out of HBM), all on the
+// mi355x_hsa_datapath_mxgemm_check: an MXFP4 GEMM, scaled-MFMA chains out of HBM;
+// mi355x_hsa_datapath_mxquant_check: MFMA, on-device MX quantisation, scaled MFMA), all on the
 // device's kept queue when there is one. They share one path: Check
 // (the steps before a check's own part, the timed dispatch, the return
 // conventions), DeviceWork (the queue and executable) and Buffers (the pool
@@ -44,6 +45,7 @@
 #include "datapath_splitk_verify.h"
 #include "datapath_attn_verify.h"
 #include "datapath_mxgemm_verify.h"
+#include "datapath_mxquant_verify.h"
 #include "datapath_verify.h"
 #include "hsa_runtime.h"
 #include "probe_json.h"
@@ -906,6 +908,76 @@ extern "C" int mi355x_hsa_datapath_mxgemm_check(int ordinal, uint32_t nonce, dou
   }
   const auto t_verify = std::chrono::steady_clock::now();
   mi355x::datapath_mxgemm_verdict(records, tiles, grid, MI355X_DPMX_KSTEPS, out);
+  out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
+  return c.finish();
+}
+
+extern "C" void mi355x_hsa_datapath_mxquant_corrupt(int stage, int word, int bit, int ordinal) {
+  set_dp_corrupt("datapath_mxquant", stage, word, bit, ordinal);
+}
+
+extern "C" int mi355x_hsa_datapath_mxquant_check(int ordinal, uint32_t nonce, double timeout_s,
+                                                 mi355x_datapath_mxquant_result* out) {
+  *out = mi355x::blank_result<mi355x_datapath_mxquant_result>(ordinal, nonce);
+  out->hsteps = MI355X_DPMQ_HSTEPS;
+  Check<mi355x_datapath_mxquant_result> c(ordinal, timeout_s, out);
+  KernelInfo ks[2];  // fill, the MLP tile
+  // the operands live in device memory; records, the quantised images, Y tiles and kernargs in host pools
+  if (!c.begin(true, &mi355x_datapath_mxquant_result::grid, 1, "datapath_mxquant",
+               {{"mi355x_mxquant_fill.kd", sizeof(mi355x_datapath_mxquant_args)},
+                {"mi355x_mfma_datapath_mxquant.kd", sizeof(mi355x_datapath_mxquant_args)}},
+               ks))
+    return 1;
+  const uint32_t grid = static_cast<uint32_t>(out->grid);
+  if (!dpmq_sizes_ok(grid, MI355X_DPMQ_HSTEPS)) {
+    std::snprintf(out->error, sizeof(out->error), "datapath mxquant check: %u workgroups", grid);
+    return c.finish();
+  }
+  const size_t hidden = static_cast<size_t>(MI355X_DPMQ_HSTEPS) * MI355X_DPMQ_TILE;
+  const uint32_t img_words = MI355X_DPMQ_IMG_WORDS(MI355X_DPMQ_HSTEPS);
+  const size_t rec_bytes = static_cast<size_t>(grid) * MI355X_DPMQ_REC_WORDS * sizeof(uint32_t);
+  const size_t img_bytes = static_cast<size_t>(grid) * img_words * sizeof(uint32_t);
+  const size_t tile_bytes = static_cast<size_t>(grid) * MI355X_DPMQ_WG_WORDS * sizeof(uint32_t);
+  auto* records = c.bufs.alloc<uint32_t>(g_rt.fine, rec_bytes, "alloc records", c.ag, "allow records");
+  auto* image = c.bufs.alloc<uint32_t>(g_rt.fine, img_bytes, "alloc image", c.ag, "allow image");
+  auto* tiles = c.bufs.alloc<uint32_t>(g_rt.fine, tile_bytes, "alloc tiles", c.ag, "allow tiles");
+  // written by mi355x_mxquant_fill, whole, before the MLP tile reads them: no runtime fill or copy (ROCr would open a queue)
+  auto* x = c.bufs.alloc<uint16_t>(c.ag->coarse, static_cast<size_t>(grid) * MI355X_DPMQ_TILE * MI355X_DPMQ_TILE * 2, "alloc X");
+  auto* w1 = c.bufs.alloc<uint16_t>(c.ag->coarse, hidden * MI355X_DPMQ_TILE * 2, "alloc W1");
+  auto* w2 = c.bufs.alloc<uint8_t>(c.ag->coarse, MI355X_DPMQ_TILE * hidden / 2, "alloc W2");
+  auto* sb = c.bufs.alloc<uint8_t>(c.ag->coarse, MI355X_DPMQ_TILE * hidden / 32, "alloc W2 scales");
+  auto* kargs =
+      c.bufs.alloc<mi355x_datapath_mxquant_args>(g_rt.kernarg, kKernargBytes, "alloc kernarg", c.ag, "allow kernarg");
+  if (!c.bufs.ok()) return c.fail(c.bufs.status, c.bufs.what);
+  std::memset(records, 0, rec_bytes);
+  std::memset(image, 0xFF, img_bytes);
+  std::memset(tiles, 0xFF, tile_bytes);
+  std::memset(kargs, 0, kKernargBytes);
+  kargs->records = records;
+  kargs->tiles = tiles;
+  kargs->image = image;
+  kargs->x = x;
+  kargs->w1 = w1;
+  kargs->w2 = w2;
+  kargs->sb = sb;
+  kargs->nonce = nonce;
+  kargs->grid = grid;
+  kargs->hsteps = MI355X_DPMQ_HSTEPS;
+  if (!c.run(ks[0], kargs, grid, MI355X_DPMQ_THREADS, "datapath mxquant fill", &out->fill_us) ||
+      !c.run(ks[1], kargs, grid, MI355X_DPMQ_THREADS, "datapath mxquant check", &out->kernel_us))
+    return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_dp_corrupt_mu);
+    const int* cr = dp_corrupt("datapath_mxquant");
+    const uint32_t per_wg = cr[0] == 3 ? MI355X_DPMQ_WG_WORDS : cr[0] == 2 ? img_words : 16u;
+    if (cr[0] >= 0 && cr[0] < MI355X_DPMQ_STAGES && cr[1] >= 0 && static_cast<uint32_t>(cr[1]) < grid * per_wg &&
+        (cr[0] != 0 || cr[1] % 16 < 8) && cr[2] >= 0 && cr[2] < 32 && (cr[3] < 0 || cr[3] == ordinal))
+      (cr[0] == 3   ? tiles[cr[1]]
+       : cr[0] == 2 ? image[cr[1]]
+                    : records[(cr[1] / 16) * MI355X_DPMQ_REC_WORDS + dpmq_fold_slot(cr[0], cr[1] % 16)]) ^= 1u << cr[2];
+  }
+  const auto t_verify = std::chrono::steady_clock::now();
+  mi355x::datapath_mxquant_verdict(records, image, tiles, grid, MI355X_DPMQ_HSTEPS, out);
   out->verify_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_verify).count();
   return c.finish();
 }

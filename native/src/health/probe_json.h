@@ -133,6 +133,11 @@ inline DatapathExtras datapath_extras(const mi355x_datapath_mxgemm_result& r) {
   return {json_format("\"ksteps\":%d,", r.ksteps), "", json_format("\"fill_us\":%.2f,", r.fill_us),
           json_format("\"verify_us\":%.1f,", r.verify_us)};
 }
+// the MX quantise check's: the slab count in place of the k-steps
+inline DatapathExtras datapath_extras(const mi355x_datapath_mxquant_result& r) {
+  return {json_format("\"hsteps\":%d,", r.hsteps), "", json_format("\"fill_us\":%.2f,", r.fill_us),
+          json_format("\"verify_us\":%.1f,", r.verify_us)};
+}
 // the tile and split counts, the ledger's bad words, the fewest XCDs that served one tile, the drain's GPU time
 inline DatapathExtras datapath_extras(const mi355x_datapath_splitk_result& r) {
   return {json_format("\"tiles\":%d,\"splits\":%d,\"ksteps\":%d,", r.tiles, r.splits, r.ksteps),
@@ -182,6 +187,7 @@ inline std::string datapath_gemm_json(const mi355x_datapath_gemm_result& r) { re
 inline std::string datapath_splitk_json(const mi355x_datapath_splitk_result& r) { return datapath_device_json(r); }
 inline std::string datapath_attn_json(const mi355x_datapath_attn_result& r) { return datapath_device_json(r); }
 inline std::string datapath_mxgemm_json(const mi355x_datapath_mxgemm_result& r) { return datapath_device_json(r); }
+inline std::string datapath_mxquant_json(const mi355x_datapath_mxquant_result& r) { return datapath_device_json(r); }
 
 // phase_us of one device: HSA build = code object, queue, buffers, dispatch;
 // HIP build = hipSetDevice + identity, the stream's queue, buffers + events, dispatch

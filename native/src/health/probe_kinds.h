@@ -33,6 +33,7 @@ inline constexpr ProbeKind kProbeKinds[] = {
     {"datapath_splitk", "-splitk"},
     {"datapath_attn", "-attn"},
     {"datapath_mxgemm", "-mxgemm"},
+    {"datapath_mxquant", "-mxquant"},
 };
 inline constexpr int kProbeKindCount = static_cast<int>(sizeof(kProbeKinds) / sizeof(kProbeKinds[0]));
 

@@ -17,6 +17,7 @@
 //   mi355x-liveness-probe --datapath-splitk [--devices ..] (split-K partials summed by L2 atomics, see mi355x_mfma_datapath_splitk)
 //   mi355x-liveness-probe --datapath-attn [--devices ..] (a flash-attention loop, see mi355x_mfma_datapath_attn)
 //   mi355x-liveness-probe --datapath-mxgemm [--devices ..] (an MXFP4 GEMM out of HBM, see mi355x_mfma_datapath_mxgemm)
+//   mi355x-liveness-probe --datapath-mxquant [--devices ..] (MFMA, on-device MX quantisation, scaled MFMA, see mi355x_mfma_datapath_mxquant)
 //   mi355x-liveness-probe --peer [--devices ..] [--peer-bytes B] [--peer-reps R]
 //                                      (DMA copy over every GPU pair's link, verified)
 //   --corrupt-word K[@O] / $MI355X_PROBE_CORRUPT_FILE: debug fault injection (see refresh_fault_injection)
@@ -35,6 +36,8 @@
 //       3 = O word; W numbered over all workgroups, as first_bad_word)
 //   --corrupt-datapath-mxgemm S:W:B[@O]: the same for the MXFP4 GEMM check (S 0 = A fold, 1 = B fold, 2 = scale fold,
 //       3 = D word; W numbered over all workgroups, as first_bad_word)
+//   --corrupt-datapath-mxquant S:W:B[@O]: the same for the MX quantise check (S 0 = W1 fold, 1 = W2 / scale fold,
+//       2 = dword of the quantised image, 3 = Y word; W numbered over all workgroups, as first_bad_word)
 //
 // Built twice from this file: `mi355x-liveness-probe` launches through ROCr
 // directly (MI355X_PROBE_HSA; links only libhsa-runtime64, one AQL dispatch),
@@ -354,6 +357,7 @@ constexpr DatapathOps kDatapathOps[] = {
     MI355X_DATAPATH_OPS(datapath_fp8),    MI355X_DATAPATH_OPS(datapath_f16),    MI355X_DATAPATH_OPS(datapath_f64),
     MI355X_DATAPATH_OPS(datapath_f6f4),   MI355X_DATAPATH_OPS(datapath_sparse), MI355X_DATAPATH_OPS(datapath_gemm),
     MI355X_DATAPATH_OPS(datapath_splitk), MI355X_DATAPATH_OPS(datapath_attn),   MI355X_DATAPATH_OPS(datapath_mxgemm),
+    MI355X_DATAPATH_OPS(datapath_mxquant),
 };
 #undef MI355X_DATAPATH_OPS
 // kDatapathOps[i] belongs to kProbeKinds[i]

@@ -23,6 +23,7 @@ Outputs land inside the package so they travel with the repo snapshot:
 * ``bin/datapath_splitk_contract_cli`` and for the split-K GEMM check (testing/datapath_splitk_reference.py)
 * ``bin/datapath_attn_contract_cli`` and for the fused attention check (testing/datapath_attn_reference.py)
 * ``bin/datapath_mxgemm_contract_cli`` and for the MXFP4 GEMM pipeline check (testing/datapath_mxgemm_reference.py)
+* ``bin/datapath_mxquant_contract_cli`` and for the MX quantise check (testing/datapath_mxquant_reference.py)
 * ``bin/probe_contract_cli``      host-only driver of the probe's wire format: its reply printers and
   its server's request grammar (testing/contract_cli.py)
 
@@ -64,6 +65,7 @@ DATAPATH_GEMM_CLI = PKG_DIR / "bin" / "datapath_gemm_contract_cli"
 DATAPATH_SPLITK_CLI = PKG_DIR / "bin" / "datapath_splitk_contract_cli"
 DATAPATH_ATTN_CLI = PKG_DIR / "bin" / "datapath_attn_contract_cli"
 DATAPATH_MXGEMM_CLI = PKG_DIR / "bin" / "datapath_mxgemm_contract_cli"
+DATAPATH_MXQUANT_CLI = PKG_DIR / "bin" / "datapath_mxquant_contract_cli"
 PROBE_CONTRACT_CLI = PKG_DIR / "bin" / "probe_contract_cli"
 
 
@@ -237,7 +239,7 @@ def ensure_built(hip: bool | None = None) -> None:
         hip = hipcc_available()
     if hip in _checked:
         return
-    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI, DATAPATH_I8_CLI, DATAPATH_BF16_CLI, DATAPATH_FP8_CLI, DATAPATH_F16_CLI, DATAPATH_F64_CLI, DATAPATH_F6F4_CLI, DATAPATH_SPARSE_CLI, DATAPATH_GEMM_CLI, DATAPATH_SPLITK_CLI, DATAPATH_ATTN_CLI, DATAPATH_MXGEMM_CLI, PROBE_CONTRACT_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO, HSACO_INJECT] if hip else [])
+    targets = [NATIVE_SO, CONTRACT_CLI, DATAPATH_CLI, DATAPATH_I8_CLI, DATAPATH_BF16_CLI, DATAPATH_FP8_CLI, DATAPATH_F16_CLI, DATAPATH_F64_CLI, DATAPATH_F6F4_CLI, DATAPATH_SPARSE_CLI, DATAPATH_GEMM_CLI, DATAPATH_SPLITK_CLI, DATAPATH_ATTN_CLI, DATAPATH_MXGEMM_CLI, DATAPATH_MXQUANT_CLI, PROBE_CONTRACT_CLI] + ([HIP_SO, PROBE_EXE, PROBE_EXE_HIP, MOUNTEMU_EXE, HIP_DEVEMU_EXE, HSACO, HSACO_INJECT] if hip else [])
     if not _up_to_date(targets, hip):
         BUILD_DIR.mkdir(parents=True, exist_ok=True)
         with open(BUILD_DIR.parent / ".build.lock", "w") as lk:

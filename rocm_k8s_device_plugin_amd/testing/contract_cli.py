@@ -206,6 +206,31 @@ def datapath_mxgemm_verdict(cli, image: bytes, grid: int, nonce: int, ksteps: in
                           text=True, timeout=120)
 
 
+def datapath_mxquant_cli(build_dir: Path) -> Path:
+    """native/tests/datapath_mxquant_contract_cli.cpp, found or compiled like contract_cli()."""
+    from .. import _build
+    exe = _build.DATAPATH_MXQUANT_CLI
+    if os.access(exe, os.X_OK) and (_build._up_to_date([exe]) or not host_compiler()):
+        return exe
+    return compile_cli(Path(build_dir) / "datapath_mxquant_contract_cli",
+                       source=REPO / "native" / "tests" / "datapath_mxquant_contract_cli.cpp")
+
+
+def datapath_mxquant_image(cli, grid: int, nonce: int, hsteps: int, command: str = "image") -> bytes:
+    """`datapath_mxquant_contract_cli image` (or `operands`): the header's records, quantised images and Y tiles (operands)."""
+    return subprocess.run([str(cli), command, str(grid), str(nonce), str(hsteps)], capture_output=True, check=True,
+                          timeout=120).stdout
+
+
+def datapath_mxquant_verdict(cli, image: bytes, grid: int, nonce: int, hsteps: int, work) -> subprocess.CompletedProcess:
+    """`datapath_mxquant_contract_cli verdict` on `image`, written into the directory `work`: stdout is one
+    datapath_mxquant_json line; exit 2 and no line for an image of another length."""
+    path = Path(work) / "datapath_mxquant_image.bin"
+    path.write_bytes(image)
+    return subprocess.run([str(cli), "verdict", str(grid), str(nonce), str(hsteps), str(path)], capture_output=True,
+                          text=True, timeout=120)
+
+
 def datapath_splitk_cli(build_dir: Path) -> Path:
     """native/tests/datapath_splitk_contract_cli.cpp, found or compiled like contract_cli()."""
     from .. import _build

@@ -33,6 +33,7 @@ from . import datapath_gemm_reference as dpgm
 from . import datapath_splitk_reference as dpsk
 from . import datapath_attn_reference as dpat
 from . import datapath_mxgemm_reference as dpmx
+from . import datapath_mxquant_reference as dpmq
 from . import datapath_reference as dp
 from . import kernel_reference as ref
 
@@ -62,12 +63,12 @@ KEYS = {"sweep": SWEEP_KEYS, "perf": PERF_KEYS, "datapath": DATAPATH_KEYS, "data
         "datapath_f64": DATAPATH_KEYS, "datapath_f6f4": DATAPATH_KEYS, "datapath_sparse": DATAPATH_KEYS,
         "datapath_gemm": DATAPATH_KEYS, "datapath_splitk": DATAPATH_KEYS + ("tiles", "splits", "ledger_bad"),
         "datapath_attn": DATAPATH_KEYS + ("heads", "qblocks", "kblocks", "exp_inexact"),
-        "datapath_mxgemm": DATAPATH_KEYS + ("ksteps",)}
+        "datapath_mxgemm": DATAPATH_KEYS + ("ksteps",), "datapath_mxquant": DATAPATH_KEYS + ("hsteps",)}
 MODES = {"sweep": SWEEP_MODES, "perf": PERF_MODES, "datapath": DATAPATH_MODES, "datapath_i8": DATAPATH_MODES,
          "datapath_bf16": DATAPATH_MODES, "datapath_fp8": DATAPATH_MODES, "datapath_f16": DATAPATH_MODES,
          "datapath_f64": DATAPATH_MODES, "datapath_f6f4": DATAPATH_MODES, "datapath_sparse": DATAPATH_MODES,
          "datapath_gemm": DATAPATH_MODES, "datapath_splitk": DATAPATH_MODES, "datapath_attn": DATAPATH_MODES,
-         "datapath_mxgemm": DATAPATH_MODES}
+         "datapath_mxgemm": DATAPATH_MODES, "datapath_mxquant": DATAPATH_MODES}
 
 # the clocks and times behind the stub's throughput figures (MHz, us)
 CLOCK_MHZ, SLOW_XCD, SLOW_XCD_MHZ = 1530, 3, 510
@@ -294,6 +295,30 @@ def datapath_mxgemm_replies(build_dir) -> list:
     return out
 
 
+def datapath_mxquant_replies(build_dir) -> list:
+    """As datapath_mxgemm_replies for the MX quantise check at the production shape: stuck_bit is bit 30 of every Y word
+    of row 0 of one workgroup; device_bad: that workgroup's first W1 fold sum is off by 12."""
+    cli = contract_cli.datapath_mxquant_cli(build_dir)
+    healthy = np.frombuffer(contract_cli.datapath_mxquant_image(cli, GRID, NONCE, dpmq.HSTEPS), dtype="<u4")
+    cut = np.cumsum([GRID * dpmq.REC_WORDS, GRID * dpmq.img_words(dpmq.HSTEPS)])
+    out = []
+    for mode in MODES["datapath_mxquant"]:
+        recs, images, tiles = (part.reshape(GRID, -1).copy() for part in np.split(healthy, cut))
+        if mode == "stuck_bit":
+            tiles[WG, :dpmq.TILE] &= np.uint32(~(1 << BIT) & 0xFFFFFFFF)
+        elif mode == "missing":
+            recs[WG:WG + 2, :] = 0
+        elif mode == "device_bad":
+            recs[WG, dpmq.fold_slot(0, 1)] += 12
+        else:
+            assert mode == "ok", mode
+        r = contract_cli.datapath_mxquant_verdict(cli, dpmq.image_bytes(recs, images, tiles), GRID, NONCE, dpmq.HSTEPS,
+                                                  build_dir)
+        assert r.returncode == 0, r.stderr
+        out.append(json.loads(r.stdout))
+    return out
+
+
 def datapath_splitk_replies(build_dir) -> list:
     """As datapath_gemm_replies for the split-K check at the production sizes (GRID / 8 tiles, 8 splits of 4 k-steps).
     stuck_bit: bit 30 of every D word of row 0 of tile WG; missing: workgroups WG and WG + 1 (both of tile WG // 8)
@@ -377,6 +402,8 @@ def real_replies(kind: str, build_dir) -> dict:
         out = datapath_attn_replies(build_dir)
     elif kind == "datapath_mxgemm":
         out = datapath_mxgemm_replies(build_dir)
+    elif kind == "datapath_mxquant":
+        out = datapath_mxquant_replies(build_dir)
     elif kind == "datapath_bf16":
         out = dpbf.verdicts(dpbf.contract_cli(build_dir), [datapath_bf16_case(m) for m in modes], len(modes))
     else:

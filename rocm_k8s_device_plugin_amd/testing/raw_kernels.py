@@ -41,6 +41,12 @@ REQUESTS.json is a list of requests, run in order:
         {"kind": "hbm", "wg", "index": byte of A, "mask"} or {"kind": "scale", "wg", "wave", "lane",
         "index": step * 16 + sub-step * 4 + scale VGPR, "mask"})
 
+    {"id": ..., "kernel": "datapath_mxquant", "nonce": n, "grid": g, "hsteps": h[, "launch_grid": ...]}
+        (mi355x_mxquant_fill, then mi355x_mfma_datapath_mxquant, on the same arguments; with the inject build "inject" is
+        {"kind": "h", "wg", "wave", "lane", "index": slab * 64 + block * 16 + register, "mask"}, {"kind": "q", "wg", "step",
+        "index": dword of the Q tile, "mask"}, {"kind": "scale", "wg", "wave", "lane", "index": slab * 8 + sub-step * 4 +
+        scale VGPR, "mask"} or {"kind": "mfma", "wg", "wave", "lane", "index", "mask"})
+
 A sweep, datapath, datapath_i8, datapath_bf16, datapath_fp8, datapath_f16, datapath_f64, datapath_f6f4 or datapath_sparse request may add "code_object": "inject": the kernel then comes from
 liveness_gfx950_inject.hsaco, the test-only build of the same sources whose argument structs end in
 the injection fields (MI355X_TEST_INJECT in liveness_kernel.h / datapath_kernel.h / datapath_i8_kernel.h /
@@ -290,6 +296,21 @@ class DatapathMxgemmInjectArgs(ctypes.Structure):
 DATAPATH_MXGEMM_ARG_STRUCTS = {"mi355x_datapath_mxgemm_args": DatapathMxgemmArgs}
 DATAPATH_MXGEMM_INJECT_ARG_STRUCTS = {"mi355x_datapath_mxgemm_args": DatapathMxgemmInjectArgs}
 DATAPATH_MXGEMM_INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2, "hbm": 3, "scale": 4}   # MI355X_DPMX_INJECT_*
+
+
+class DatapathMxquantArgs(ctypes.Structure):
+    _fields_ = [("records", _ptr), ("tiles", _ptr), ("image", _ptr), ("x", _ptr), ("w1", _ptr), ("w2", _ptr), ("sb", _ptr),
+                ("nonce", _u32), ("grid", _u32), ("hsteps", _u32), ("pad", _u32)]
+
+
+class DatapathMxquantInjectArgs(ctypes.Structure):
+    _fields_ = DatapathMxquantArgs._fields_ + _INJECT_FIELDS
+
+
+# the mirrors of datapath_mxquant_kernel.h; both kernels of the check take the one struct
+DATAPATH_MXQUANT_ARG_STRUCTS = {"mi355x_datapath_mxquant_args": DatapathMxquantArgs}
+DATAPATH_MXQUANT_INJECT_ARG_STRUCTS = {"mi355x_datapath_mxquant_args": DatapathMxquantInjectArgs}
+DATAPATH_MXQUANT_INJECT_KINDS = {"none": 0, "h": 1, "q": 2, "scale": 3, "mfma": 4}   # MI355X_DPMQ_INJECT_*
 INJECT_KINDS = {"none": 0, "mfma": 1, "lds": 2}      # MI355X_INJECT_*; the datapath kernel knows none and mfma
 CODE_OBJECTS = ("production", "inject")
 
@@ -304,6 +325,9 @@ def inject_words(req: dict) -> tuple:
                 int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
     if req["kernel"] == "datapath_mxgemm":               # likewise
         return (DATAPATH_MXGEMM_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj.get("wave", inj.get("step", 0))),
+                int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
+    if req["kernel"] == "datapath_mxquant":              # likewise: the slab of a q injection
+        return (DATAPATH_MXQUANT_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj.get("wave", inj.get("step", 0))),
                 int(inj.get("lane", 0)), int(inj["index"]), int(inj["mask"]) & 0xFFFFFFFF)
     if req["kernel"] == "datapath_splitk":
         return (DATAPATH_SPLITK_INJECT_KINDS[inj["kind"]], int(inj["wg"]), int(inj["wave"]), int(inj["lane"]),
@@ -326,7 +350,7 @@ def code_object_of(req: dict) -> str:
     if which == "inject" and req["kernel"] not in ("sweep", "datapath", "datapath_i8", "datapath_bf16", "datapath_fp8",
                                                    "datapath_f16", "datapath_f64", "datapath_f6f4",
                                                    "datapath_sparse", "datapath_gemm", "datapath_splitk",
-                                                   "datapath_attn", "datapath_mxgemm"):
+                                                   "datapath_attn", "datapath_mxgemm", "datapath_mxquant"):
         raise ValueError(f"the inject build has no hook in {req['kernel']!r}")
     if which != "inject" and "inject" in req:
         raise ValueError("an injection needs \"code_object\": \"inject\"")
@@ -347,10 +371,12 @@ KERNELS = {"liveness": ("mi355x_mfma_liveness", 64), "sweep": ("mi355x_chip_swee
            "datapath_gemm": ("mi355x_mfma_datapath_gemm", 256),
            "datapath_splitk": ("mi355x_mfma_datapath_splitk", 256),
            "datapath_attn": ("mi355x_mfma_datapath_attn", 256),
-           "datapath_mxgemm": ("mi355x_mfma_datapath_mxgemm", 256)}
+           "datapath_mxgemm": ("mi355x_mfma_datapath_mxgemm", 256),
+           "datapath_mxquant": ("mi355x_mfma_datapath_mxquant", 256)}
 # kernel -> (symbol, lanes) of a kernel launched before it (FIRST) or after it (LAST), on the same arguments and workgroups
 FIRST = {"datapath_gemm": ("mi355x_gemm_fill", 256), "datapath_splitk": ("mi355x_splitk_fill", 256),
-         "datapath_attn": ("mi355x_attn_fill", 256), "datapath_mxgemm": ("mi355x_mxgemm_fill", 256)}
+         "datapath_attn": ("mi355x_attn_fill", 256), "datapath_mxgemm": ("mi355x_mxgemm_fill", 256),
+         "datapath_mxquant": ("mi355x_mxquant_fill", 256)}
 LAST = {"datapath_splitk": ("mi355x_splitk_drain", 256)}
 
 _H2D, _D2H = 1, 2
@@ -615,6 +641,24 @@ def plan(req: dict, base_dir: Path):
         cls, tail = (DatapathMxgemmInjectArgs, inject_words(req)) if inject else (DatapathMxgemmArgs, ())
         return bufs, lambda p: cls(p["records"], p["tiles"], p["a"], p["b"], p["sa"], p["sb"], req["nonce"], g, ksteps, 0,
                                    *tail), wgs
+    if k == "datapath_mxquant":
+        g, hsteps = int(req["grid"]), int(req["hsteps"])
+        if not 1 <= g <= 1024 or not 1 <= hsteps <= 4:
+            raise ValueError("grid outside 1..1024 or hsteps outside 1..4")   # the buffers are sized by them
+        bufs = [("records", np.uint32, _filled(g * 32 * 4, OUT_PREFILL)),
+                ("tiles", np.uint32, _filled(g * 128 * 128 * 4, OUT_PREFILL)),
+                ("image", np.uint32, _filled(g * 2176 * hsteps * 4, OUT_PREFILL)),
+                ("x", np.uint16, _filled(g * 128 * 128 * 2, OUT_PREFILL)),
+                ("w1", np.uint16, _filled(128 * hsteps * 128 * 2, OUT_PREFILL)),
+                ("w2", np.uint8, _filled(128 * hsteps * 64, OUT_PREFILL)),
+                ("sb", np.uint8, _filled(128 * hsteps * 4, OUT_PREFILL))]
+        inject = code_object_of(req) == "inject"
+        wgs = g if inject else int(req.get("launch_grid", g))
+        if wgs < g:
+            raise ValueError("launch_grid below grid")
+        cls, tail = (DatapathMxquantInjectArgs, inject_words(req)) if inject else (DatapathMxquantArgs, ())
+        return bufs, lambda p: cls(p["records"], p["tiles"], p["image"], p["x"], p["w1"], p["w2"], p["sb"], req["nonce"], g,
+                                   hsteps, 0, *tail), wgs
     raise ValueError(f"unknown kernel {k!r}")
 
 

@@ -51,6 +51,8 @@ Split-K GEMM check replies ("datapath_splitk" requests /
 --datapath-splitk) follow the "datapath_splitk" map and append "datapath_splitk:<host ordinal>".
 MXFP4 GEMM pipeline-check replies ("datapath_mxgemm" requests /
 --datapath-mxgemm) follow the "datapath_mxgemm" map and append "datapath_mxgemm:<host ordinal>".
+MX quantise check replies ("datapath_mxquant" requests /
+--datapath-mxquant) follow the "datapath_mxquant" map and append "datapath_mxquant:<host ordinal>".
 Fused attention check replies ("datapath_attn" requests /
 --datapath-attn) follow the "datapath_attn" map and append "datapath_attn:<host ordinal>".
 Each iteration count it is asked for (a "probe" / "sweep" request line, or
@@ -109,7 +111,7 @@ def _device(ordinal_reported, mode, nonce, host_ordinal=None, iters=4):
 
 DATAPATH_KINDS = ("datapath", "datapath_i8", "datapath_bf16", "datapath_fp8", "datapath_f16", "datapath_f64",
                   "datapath_f6f4", "datapath_sparse", "datapath_gemm", "datapath_splitk", "datapath_attn",
-                  "datapath_mxgemm")
+                  "datapath_mxgemm", "datapath_mxquant")
 
 
 def _log_check(kind, host_ordinal):
@@ -423,6 +425,35 @@ def _datapath_mxgemm_device(ordinal_reported, mode, nonce, host_ordinal=None):
     return d
 
 
+# the shipped verdict's figures for the mxquant kind's faults at nonce 0x5EED142F (testing/probe_contract.py builds them):
+# stuck_bit = bit 30 of the 128 Y words of row 0 of workgroup 17 (its first word's healthy value), device_bad = fold
+# word 1 of the W1 feed of workgroup 17 off by 12 (its healthy value)
+STUCK_MXQUANT = (128, 17 * 16384, 1358491952)
+FEED_MXQUANT = (17 * 16 + 1, 3800796528)
+
+
+def _datapath_mxquant_device(ordinal_reported, mode, nonce, host_ordinal=None):
+    """MX quantise check reply (kind "datapath_mxquant"; stages: W1 feed, W2 and scale feed, quantised image, Y words);
+    the modes of _datapath_device, from the control file's "datapath_mxquant" map."""
+    stuck = dict(records_ok=255, tile_bad=STUCK_MXQUANT[0], stage_bad=[0, 0, 0, STUCK_MXQUANT[0]], first_bad_wg=17,
+                 first_bad_stage=3, first_bad_word=STUCK_MXQUANT[1], first_bad_got=STUCK_MXQUANT[2] ^ 0x40000000,
+                 first_bad_want=STUCK_MXQUANT[2], first_bad_xor=0x40000000,
+                 error=f"255/256 workgroups exact (feed_bad=0 quant_bad=0 y_bad={STUCK_MXQUANT[0]}); first bad: wg 17 "
+                       f"stage 3 word {STUCK_MXQUANT[1]} xor 0x40000000 (bit 30)")
+    d = _datapath_reply(ordinal_reported, "ok" if mode == "device_bad" else mode, nonce, host_ordinal, 4, stuck, 150.0,
+                        40000.0, kind="datapath_mxquant")
+    d.update(hsteps=4, fill_us=30.0, verify_us=30000.0)
+    if mode == "missing":
+        d.update(error="254/256 workgroups exact (feed_bad=0 quant_bad=0 y_bad=0)")
+    elif mode == "device_bad":
+        d.update(ok=False, records_ok=255, mfma_bad=1, stage_bad=[1, 0, 0, 0], first_bad_wg=17, first_bad_stage=0,
+                 first_bad_word=FEED_MXQUANT[0], first_bad_got=FEED_MXQUANT[1] + 12, first_bad_want=FEED_MXQUANT[1],
+                 first_bad_xor=12,
+                 error=f"255/256 workgroups exact (feed_bad=1 quant_bad=0 y_bad=0); first bad: wg 17 stage 0 word "
+                       f"{FEED_MXQUANT[0]} xor 0x0000000c")
+    return d
+
+
 CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datapath_device,
                 "datapath_i8": _datapath_i8_device, "datapath_bf16": _datapath_bf16_device,
                 "datapath_fp8": _datapath_fp8_device,
@@ -433,7 +464,8 @@ CHECK_DEVICE = {"sweep": _sweep_device, "perf": _perf_device, "datapath": _datap
                 "datapath_gemm": _datapath_gemm_device,
                 "datapath_splitk": _datapath_splitk_device,
                 "datapath_attn": _datapath_attn_device,
-                "datapath_mxgemm": _datapath_mxgemm_device}
+                "datapath_mxgemm": _datapath_mxgemm_device,
+                "datapath_mxquant": _datapath_mxquant_device}
 
 
 def _blank(kind, ordinal_reported, nonce=0):
@@ -513,6 +545,7 @@ _HEADS = (("perf", (_INT, _FLOAT, _UINT0)), ("datapath_i8", (_FLOAT,)), ("datapa
           ("datapath_splitk", (_FLOAT,)),
           ("datapath_attn", (_FLOAT,)),
           ("datapath_mxgemm", (_FLOAT,)),
+          ("datapath_mxquant", (_FLOAT,)),
           ("datapath", (_FLOAT,)),
           ("sweep", (_INT, _FLOAT)), ("probe", (_INT, _FLOAT)))
 _DEVICE = re.compile(_INT + ":" + _UINT0 + "(?::" + _FLOAT + ")?")
@@ -811,6 +844,7 @@ def main(argv):
                        ("--datapath-splitk", "datapath_splitk"),
                        ("--datapath-attn", "datapath_attn"),
                        ("--datapath-mxgemm", "datapath_mxgemm"),
+                       ("--datapath-mxquant", "datapath_mxquant"),
                        ("--sweep", "sweep")):
         if flag not in argv:
             continue
